@@ -2,6 +2,15 @@
 """bench.py — GraphTrans training-step throughput on MI355X (driver contract).
 
     python bench.py [--gpus N --steps K --warmup W] [--workload code2|molpcba|nci1|er|code2-pna] [--mode mixed|bf16|fp32]
+                    [--dump-outputs DIR] [--full]
+
+A plain run sets up, warms up, times the K steps and prints the JSON line (contract keys, config, host enqueue time).
+`--dump-outputs DIR` also writes what the last timed step computed (rank 0): the loss, the model outputs, and the
+parameters and gradients after that step, as DIR/<name>.npy in float32 (large tensors as a fixed, seeded sample of their
+elements; 64 MB at most in all).  The inputs are seeded: the same arguments give the same inputs in every run.
+`--full` adds everything else described below (kernel roofline, idle-device host time, the other precision modes,
+the precision report, aggregate stress, collation, the CPU baseline, the other scaling for N > 1, bench_report.json);
+`--no-extra`, `--no-cpu-baseline`, `--no-kernel-timing` and `--cpu-baseline-full` select within it.
 
 `--gpus N` with N > 1 and no WORLD_SIZE in the environment re-executes itself under `torch.distributed.run` with N ranks
 (one per GPU, RCCL); the driver's own `python -m torch.distributed.run ... bench.py --gpus N` works as before.
@@ -22,7 +31,7 @@ Precision modes (`config.mode`):
          -- what BASELINE.json's north_star sanctions;
   bf16:  bf16 MFMA for every GEMM (fp32 storage and master weights on the GNN side);
   fp32:  fp32-accurate GEMMs everywhere (fp32 token rows).
-Rank 0 prints ONE JSON line of at most 4 KB (compact_line) with the contract keys plus
+Rank 0 prints ONE JSON line of at most 4 KB (compact_line) with the contract keys, and with --full also
   "roofline":     the dominant hand-written kernel, named as rocprofv3 names it (the kernel family with the largest total
                   HIP-event time inside the timed region; forward and dX launches of one kernel are one family): algorithmic
                   bytes|flops per launch (SURVEY.md 8d formulas) / average launch time; "traffic" = PMC bytes of the same
@@ -533,16 +542,53 @@ def precision_vs_oracle(workload, modes, device, graphs=None):
 
 
 # ---- one timed measurement ------------------------------------------------------------------------------------------
-def measure(opt, mode, scaling, world, rank, device, want_kernels=True):
-    """Build the model of `mode`, run opt.warmup + opt.steps steps, return (result dict for rank 0, model, args)."""
+def measure(opt, mode, scaling, world, rank, device, want_kernels=True, dump_dir=None):
+    """Build the model of `mode`, run opt.warmup + opt.steps steps, return (result dict for rank 0, model, args).
+    dump_dir: rank 0 writes what the last timed step computed there (dump_outputs)."""
     import gc
     try:
-        return _measure(opt, mode, scaling, world, rank, device, want_kernels)
+        return _measure(opt, mode, scaling, world, rank, device, want_kernels, dump_dir)
     finally:
         gc.unfreeze()   # _measure freezes the set-up heap after its warm-up: undone on every way out (a raise included)
 
 
-def _measure(opt, mode, scaling, world, rank, device, want_kernels):
+DUMP_OUT_ELEMS = 8 << 20     # --dump-outputs: float32 elements for the model outputs (32 MB) ...
+DUMP_PARAM_ELEMS = 6 << 20   # ... and for the parameters and gradients together (24 MB); the loss is one more
+
+
+def _dump_array(path_dir, name, t, cap):
+    """t as float32 DIR/<name>.npy; above `cap` elements, a fixed sample: flat indices drawn without replacement by a
+    generator seeded from the name and the size, in increasing order (the same elements in every run)."""
+    import zlib
+    a = t.detach().float().cpu().numpy().reshape(-1) if t.dim() != 0 else t.detach().float().cpu().numpy()
+    if a.size > cap:
+        rng = np.random.default_rng(zlib.crc32(("%s:%d" % (name, a.size)).encode()))
+        a = a[np.sort(rng.choice(a.size, size=cap, replace=False))]
+    elif t.dim() != 0:
+        a = a.reshape(tuple(t.shape))
+    np.save(os.path.join(path_dir, name + ".npy"), np.asarray(a, dtype=np.float32))
+    return a.nbytes
+
+
+def dump_outputs(path_dir, loss, out, model):
+    """What a caller of the timed step receives from its last call: the loss, the model outputs (one array per
+    prediction head), and the parameters after the optimizer step with the gradients they were stepped on."""
+    os.makedirs(path_dir, exist_ok=True)
+    outs = list(out) if isinstance(out, (list, tuple)) else [out]
+    total = _dump_array(path_dir, "loss", loss, 1)
+    for i, o in enumerate(outs):
+        total += _dump_array(path_dir, "output" if len(outs) == 1 else "output_%d" % i, o, DUMP_OUT_ELEMS // len(outs))
+    named = [(k, p) for k, p in model.named_parameters()]
+    cap = max(1, DUMP_PARAM_ELEMS // (2 * max(len(named), 1)))
+    for k, p in named:
+        total += _dump_array(path_dir, "param." + k, p, cap)
+        if p.grad is not None:
+            total += _dump_array(path_dir, "grad." + k, p.grad, cap)
+    assert total <= 64 << 20, total
+    return total
+
+
+def _measure(opt, mode, scaling, world, rank, device, want_kernels, dump_dir):
     import torch.distributed as dist
 
     from graphtrans_amd import _lib
@@ -585,7 +631,9 @@ def _measure(opt, mode, scaling, world, rank, device, want_kernels):
         store = make_store(opt.workload, 4 * per_gpu, 1000 * rank)
         sampler = np.random.default_rng(rank)
 
-    def step(i):
+    last = {}
+
+    def step(i, keep=False):
         if store is not None:
             b = store.collate(sampler.permutation(len(store))[:per_gpu])
         else:
@@ -598,6 +646,8 @@ def _measure(opt, mode, scaling, world, rank, device, want_kernels):
         sync.finish()
         if not opt.no_optimizer:
             optim.step()
+        if keep:
+            last["out"] = out
         return loss
 
     def barrier():
@@ -618,7 +668,7 @@ def _measure(opt, mode, scaling, world, rank, device, want_kernels):
     # HIP events around the aggregate / attention / linear launches of every 24th timed step (each event pair
     # costs ~3 us of stream time and the dW GEMMs stay on the main stream while bracketed, i.e. nothing overlaps them: a
     # sampled step is ~30 % slower; sampling keeps the timed region within ~2 % of a run with --no-kernel-timing)
-    timing = want_kernels and not opt.no_kernel_timing
+    timing = want_kernels and opt.full and not opt.no_kernel_timing
     off = 8 if opt.steps > 8 else opt.steps // 2   # short runs still get one sampled step
     sample = (lambda i: i % 24 == off) if timing else (lambda i: False)
     L = _lib.lib()
@@ -633,7 +683,7 @@ def _measure(opt, mode, scaling, world, rank, device, want_kernels):
         marks[i].record(cur)
         if sample(i):
             L.gt_profile_resume(PROF_MASK)
-        loss = step(opt.warmup + i)
+        loss = step(opt.warmup + i, keep=dump_dir is not None and i == opt.steps - 1)
         if sample(i):
             L.gt_profile_resume(0)
     marks[opt.steps].record(cur)
@@ -647,17 +697,20 @@ def _measure(opt, mode, scaling, world, rank, device, want_kernels):
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
     final_loss = float(loss.item())
+    if dump_dir is not None and rank == 0:
+        dump_outputs(dump_dir, loss, last.pop("out"), model)
     # the host's own cost of a step: enqueue time measured from an IDLE device, one step at a time (in the timed loop above a
     # GPU-bound step makes the host wait for queue space, so host_enqueue_ms_per_step there is bounded below by the device time)
+    # (--full only)
     idle = []
-    for i in range(min(12, max(opt.steps, 1))):
+    for i in range(min(12, max(opt.steps, 1)) if opt.full else 0):
         torch.cuda.synchronize()
         t1 = time.perf_counter()
         step(opt.warmup + opt.steps + i)
         idle.append(time.perf_counter() - t1)
     torch.cuda.synchronize()
     idle.sort()
-    host_idle_ms = 1e3 * idle[len(idle) // 2]
+    host_idle_ms = 1e3 * idle[len(idle) // 2] if idle else None
     dp_stats = dict(sync.stats)
     step_ms = sorted(marks[i].elapsed_time(marks[i + 1]) for i in range(opt.steps) if not sample(i))
     res = None
@@ -687,7 +740,7 @@ def _measure(opt, mode, scaling, world, rank, device, want_kernels):
                        "batchnorm": "synchronised over the ranks (statistics of the global batch)" if sync_bn else "per-rank statistics",
                        "interpreter": "gc.freeze() after warm-up (set-up heap out of the cyclic collector's full passes)"},
             "final_loss": round(final_loss, 5), "host_enqueue_ms_per_step": round(1e3 * t_enqueued / opt.steps, 3),
-            "host_enqueue_ms_per_step_idle_device": round(host_idle_ms, 3),
+            "host_enqueue_ms_per_step_idle_device": round(host_idle_ms, 3) if host_idle_ms is not None else None,
         }
         if world > 1:
             import torch.distributed as dist
@@ -866,7 +919,12 @@ def main():
                     help="weak (the headline): --batch graphs on EVERY GPU; strong: --batch is the global batch, split evenly "
                          "over the GPUs (b256 -> 32 graphs per GPU at 8).  With N > 1 the other one is measured too and "
                          'reported as "strong_scaling" / "weak_scaling" in the same JSON line')
-    ap.add_argument("--no-extra", action="store_true", help="only the headline measurement (no other modes / scaling / precision report)")
+    ap.add_argument("--full", action="store_true",
+                    help="everything beyond the headline: kernel roofline, idle-device host time, the other precision modes and "
+                         "scaling, the precision report, aggregate stress, collation, the CPU baseline, bench_report.json")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="write the last timed step's loss, model outputs, parameters and gradients as DIR/<name>.npy (float32)")
+    ap.add_argument("--no-extra", action="store_true", help="with --full: only the headline measurement (no other modes / scaling / precision report)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--cpu-baseline-full", action="store_true", help="BASELINE.md section 3 in full (minutes of CPU time) instead of the bounded sample")
     ap.add_argument("--no-sync-bn", action="store_true", help="strong scaling with per-rank BatchNorm statistics (default: synchronised)")
@@ -932,7 +990,7 @@ def main():
     if opt.gpus != world and rank == 0 and world > 1:
         print(f"warning: --gpus {opt.gpus} but WORLD_SIZE {world}", file=sys.stderr)
 
-    head, model, args, per_gpu = measure(opt, opt.mode, opt.scaling, world, rank, device)
+    head, model, args, per_gpu = measure(opt, opt.mode, opt.scaling, world, rank, device, dump_dir=opt.dump_outputs)
     res = None
     if rank == 0:
         metric = "graphs/sec (fwd+bwd) OGBG-Code2 GCN-Virtual b256" if opt.workload == "code2" else f"graphs/sec (fwd+bwd) {opt.workload}"
@@ -943,7 +1001,7 @@ def main():
                "ms_per_step": head["ms_per_step"], "higher_is_better": True, "scaling": opt.scaling, "vs_baseline": None,
                "dtype": head["dtype"], "data": "synthetic"}
         res.update({k: v for k, v in head.items() if k not in res})
-    extra = not opt.no_extra
+    extra = opt.full and not opt.no_extra
     if extra and world > 1:   # the other scaling of the same step, same ranks
         other = "strong" if opt.scaling == "weak" else "weak"
         del model
@@ -987,7 +1045,7 @@ def main():
             res["aggregate_stress"] = aggregate_stress_report(device)
         except Exception as e:
             res["aggregate_stress"] = {"error": repr(e)}
-    if rank == 0:
+    if rank == 0 and opt.full:
         if opt.workload in RAW_GEN:
             res["collate"] = collate_report(opt.workload, per_gpu, with_cpu=(world == 1 and not opt.no_cpu_baseline))
         if world == 1 and not opt.no_cpu_baseline:
@@ -1000,7 +1058,12 @@ def main():
                                                   f"{b['timed_iterations']} after 2 warm-ups, best of the thread counts below", full=full)
             else:
                 res["cpu_baseline"] = cpu_baseline(opt.workload, model, args, full_graphs=per_gpu)
-        emit(res, opt.report)
+    if rank == 0:
+        if opt.full or opt.report:
+            emit(res, opt.report)
+        else:   # a plain run: the line alone
+            sys.stdout.flush()
+            print(compact_line(res), flush=True)
     if world > 1:
         import torch.distributed as dist
         try:

@@ -95,3 +95,34 @@ def test_pooled_kernel_names_match_rocprof_rows():
     assert fam["k_lin3r"]["calls"] == 2 and abs(fam["k_lin3r"]["avg_us"] - 45.0) < 1e-6
     per = bench.kernel_report(recs, 1.0, torch.bfloat16, torch.float32)
     assert {"k_lin3r[fwd]", "k_lin3r[dx]"} <= set(per)
+
+
+def test_dump_outputs_writes_float32_arrays_with_a_fixed_sample(tmp_path, monkeypatch):
+    """--dump-outputs: loss, one array per output, parameters and gradients as float32 .npy; a tensor above its share of
+    the budget is written as the same seeded sample of its elements in every run, and the whole dump stays under 64 MB."""
+    import numpy as np
+    import torch
+    monkeypatch.setattr(bench, "DUMP_OUT_ELEMS", 64)
+    monkeypatch.setattr(bench, "DUMP_PARAM_ELEMS", 400)
+    torch.manual_seed(0)
+    model = torch.nn.Sequential(torch.nn.Linear(16, 32), torch.nn.Linear(32, 3))
+    x = torch.randn(20, 16)
+    out = [model(x), model(x).double()]
+    loss = sum(o.float().square().mean() for o in out)
+    loss.backward()
+    runs = []
+    for d in ("a", "b"):
+        total = bench.dump_outputs(str(tmp_path / d), loss, out, model)
+        assert 0 < total <= 64 << 20
+        runs.append({f: np.load(tmp_path / d / f) for f in sorted(os.listdir(tmp_path / d))})
+    a, b = runs
+    assert set(a) == {"loss.npy", "output_0.npy", "output_1.npy"} | {p + k + ".npy" for p in ("param.", "grad.")
+                                                                      for k in ("0.weight", "0.bias", "1.weight", "1.bias")}
+    assert all(v.dtype == np.float32 for v in a.values())
+    assert a["loss.npy"].shape == () and float(a["loss.npy"]) == np.float32(float(loss))
+    assert a["output_0.npy"].shape == (32,) and a["param.1.bias.npy"].shape == (3,) and a["grad.0.weight.npy"].shape == (50,)
+    full = model[0].weight.grad.numpy().reshape(-1)
+    assert np.isin(a["grad.0.weight.npy"], full).all() and len(np.unique(a["grad.0.weight.npy"])) == 50
+    assert np.array_equal(a["grad.1.bias.npy"], model[1].bias.grad.numpy())
+    for k in a:
+        assert np.array_equal(a[k], b[k]), k

@@ -5,6 +5,6 @@ for round in 1 2 3; do
   for kv in $LIBS; do
     v=${kv%%=*}; p=${kv#*=}
     unset GT_LIB_PATH; [ -n "$p" ] && export GT_LIB_PATH=$p
-    python bench.py --steps 100 --warmup 10 --no-kernel-timing --no-cpu-baseline --no-extra --report /tmp/ab_report.json "$@" 2>/dev/null | tail -1 | python -c "import sys,json; d=json.loads(sys.stdin.read()); print('$v', d['value'], d['ms_per_step'], d.get('host_enqueue_ms_per_step_idle_device'))"
+    python bench.py --full --steps 100 --warmup 10 --no-kernel-timing --no-cpu-baseline --no-extra --report /tmp/ab_report.json "$@" 2>/dev/null | tail -1 | python -c "import sys,json; d=json.loads(sys.stdin.read()); print('$v', d['value'], d['ms_per_step'], d.get('host_enqueue_ms_per_step_idle_device'))"
   done
 done

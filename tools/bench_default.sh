@@ -1,6 +1,6 @@
-# usage (GPU box): bash tools/bench_default.sh <tag>  -- the driver's command line (python bench.py, all defaults) with its wall time
+# usage (GPU box): bash tools/bench_default.sh <tag>  -- the full bench line (python bench.py --full, all other options at their defaults) with its wall time
 cd $GRAFT_REPO_ROOT; export TMPDIR=/tmp; O=gpurun_out/${1:-r04q}; mkdir -p $O
-t0=$(date +%s); python bench.py --report $O/bench_default_report.json > $O/bench_default.json 2> $O/bench_default.err; t1=$(date +%s); echo "wall $((t1-t0)) s"
+t0=$(date +%s); python bench.py --full --report $O/bench_default_report.json > $O/bench_default.json 2> $O/bench_default.err; t1=$(date +%s); echo "wall $((t1-t0)) s"
 python - <<PY
 import json
 line=open("$O/bench_default.json").read().strip().splitlines()[-1]

@@ -2,7 +2,7 @@
 import cProfile, pstats, sys, io, os
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 sys.argv = ["bench.py", "--workload", sys.argv[1] if len(sys.argv) > 1 else "code2", "--steps", sys.argv[2] if len(sys.argv) > 2 else "60", "--warmup", "10",
-            "--no-kernel-timing", "--no-cpu-baseline", "--no-extra"]
+            "--no-kernel-timing", "--no-cpu-baseline", "--no-extra", "--full"]
 import bench
 pr = cProfile.Profile()
 pr.enable()

@@ -5,7 +5,7 @@
 cd $GRAFT_REPO_ROOT; export TMPDIR=/tmp; O=gpurun_out/${1:-r06}; mkdir -p $O
 export GT_LIB_PATH=$PWD/graphtrans_amd/libgt_skip.so
 run() { n=$1; shift; e=$1; shift
-  env $e python bench.py --steps 100 --warmup 10 --no-kernel-timing --no-cpu-baseline --no-extra --report $O/floor_$n.json "$@" 2>/dev/null | tail -1 | \
+  env $e python bench.py --full --steps 100 --warmup 10 --no-kernel-timing --no-cpu-baseline --no-extra --report $O/floor_$n.json "$@" 2>/dev/null | tail -1 | \
     python -c "import sys,json; d=json.loads(sys.stdin.read()); print('%-34s %.4f ms/step  host idle-device enqueue %.3f ms' % ('$n', d['ms_per_step'], d.get('host_enqueue_ms_per_step_idle_device') or -1))"
 }
 for w in "code2 --workload code2" "code2_b32 --workload code2 --batch 32" "molpcba --workload molpcba" "nci1 --workload nci1"; do

@@ -3,7 +3,7 @@
 cd $GRAFT_REPO_ROOT; export TMPDIR=/tmp; TAG=${1:-r04}; W=${2:-code2}; shift; shift
 O=gpurun_out/$TAG; mkdir -p $O
 rm -rf /tmp/prof_$W
-rocprofv3 --kernel-trace --stats -d /tmp/prof_$W -o res -- python bench.py --workload $W --steps 30 --warmup 10 --no-cpu-baseline --no-kernel-timing --no-extra "$@" > $O/prof_$W.log 2>&1 || true
+rocprofv3 --kernel-trace --stats -d /tmp/prof_$W -o res -- python bench.py --full --workload $W --steps 30 --warmup 10 --no-cpu-baseline --no-kernel-timing --no-extra "$@" > $O/prof_$W.log 2>&1 || true
 db=$(find /tmp/prof_$W -name "*.db" | head -1)
 python tools/rocpd_summary.py $db 52 $O/${TAG}_${W} > /dev/null 2>&1 || true
 python tools/timeline.py $db $O/${TAG}_${W}_timeline.txt 3 > /dev/null 2>&1 || true

@@ -4,7 +4,7 @@
 cd $GRAFT_REPO_ROOT; export TMPDIR=/tmp; TAG=${1:-r05a}; W=${2:-code2}; M=${3:-mixed}; shift; shift; shift
 O=gpurun_out/$TAG; mkdir -p $O
 rm -rf /tmp/prof_${W}_$M
-rocprofv3 --kernel-trace --stats -d /tmp/prof_${W}_$M -o res -- python bench.py --workload $W --mode $M --steps 30 --warmup 10 --no-cpu-baseline --no-kernel-timing --no-extra "$@" > $O/prof_${W}_$M.log 2>&1 || true
+rocprofv3 --kernel-trace --stats -d /tmp/prof_${W}_$M -o res -- python bench.py --full --workload $W --mode $M --steps 30 --warmup 10 --no-cpu-baseline --no-kernel-timing --no-extra "$@" > $O/prof_${W}_$M.log 2>&1 || true
 db=$(find /tmp/prof_${W}_$M -name "*.db" | head -1)
 python tools/rocpd_summary.py $db 52 $O/${TAG}_${W}_${M} > /dev/null 2>&1 || true
 python tools/timeline.py $db $O/${TAG}_${W}_${M}_timeline.txt 20 > /dev/null 2>&1 || true
