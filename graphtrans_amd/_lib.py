@@ -209,6 +209,7 @@ SIGNATURES = {
     "gt_model_backward": (_i, [_p, _p, _p, _p, _p, _i, _p]),
     "gt_seq_gather_cls32": (_i, [_i, _p, _p, _p, _p, _i64, _i64, _i64, _i, _i64, _p, _p]),
     "gt_colsum_f32": (_i, [_i, _p, _i64, _i64, _p, _p]),
+    "gt_attn_head_dim_ok": (_i, [_i, _i64, _i]),
     "gt_attn_fwd": (_i, [_i, _p, _p, _p, _i64, _i64, _i, _p, _i64, _i64, _i64, _p, _i64, _p, _p, _f, _f, _f, _u64, _p]),
     "gt_attn_bwd": (_i, [_i, _p, _p, _p, _p, _p, _p, _i64, _i64, _i, _p, _i64, _i64, _i64, _p, _i64, _p, _p, _f, _f, _f,
                          _u64, _p]),

@@ -22,6 +22,7 @@
 // dtype GT_F32 : v_mfma_f32_16x16x4_f32 x8 per 32-deep step: exact fp32 (fma chain), the parity mode.
 #include <cstdlib>
 #include <cstring>
+#include <type_traits>
 #include "gt_common.h"
 #include "mfma_frag.h"
 
@@ -84,7 +85,8 @@ struct AttnArgs {
   int last_only, q_last_only;
 };
 
-// head dims 8 / 16 are zero-padded to one 32-deep MFMA step (HDP); LDS rows are HDP wide + 16 B pad
+// Head dims: every multiple of 8 up to 128, each its own instantiation.  A head dim that is not a multiple of 32 is zero-padded to
+// whole 32-deep MFMA steps (HDP); LDS rows are HDP wide + 16 B pad
 __device__ __forceinline__ bool dense_masked(const AttnArgs& a, int seq, int qpos, int kp, int npos) {
   if (a.key_valid && a.key_valid[(int64_t)seq * npos + kp] == 0.f) return true;
   if (a.dense_mask && a.dense_mask[((int64_t)seq * npos + qpos) * npos + kp] == 0.f) return true;
@@ -115,15 +117,17 @@ __device__ __forceinline__ bool block_item(const AttnArgs& a, int& seq, int& til
 
 template <int HD, typename T>
 struct Lds {
-  static constexpr int HDP = HD < 32 ? 32 : HD;
+  static_assert(HD % 8 == 0 && HD >= 8 && HD <= 128, "head dims: multiples of 8 up to 128");
+  static constexpr int HDP = (HD + 31) / 32 * 32;
+  static constexpr bool PADDED = HD % 32 != 0;
   static constexpr int LD = HDP + (sizeof(T) == 2 ? 8 : 4);
 };
 
-// zero the LDS columns [HD, LD) that load_tile never writes (only needed when HD < 32)
+// zero the LDS columns [HD, LD) that the staging never writes (only needed when HD is not a whole number of 32-deep steps)
 template <typename T, int HD>
 __device__ __forceinline__ void zero_pad_cols(T* lds) {
   constexpr int LD = Lds<HD, T>::LD;
-  if constexpr (HD < 32) {
+  if constexpr (Lds<HD, T>::PADDED) {
     for (int i = threadIdx.x; i < TILE * LD; i += ATT_THREADS) lds[i] = (T)0;
   }
 }
@@ -157,6 +161,7 @@ template <typename T, int HD>
 struct TilePair {
   static constexpr int LD = Lds<HD, T>::LD;
   static constexpr int CH = HD / 8;
+  static_assert(TILE * CH <= ATT_THREADS, "one chunk per thread and operand: head dims up to 64, TilePairWide beyond");
   Frag<T> fa, fb;
   int r, col;
   bool has, ok;
@@ -202,6 +207,65 @@ struct TilePair {
     }
   }
 };
+
+// TilePair above head dim 64, where a tile is more than one 16-byte chunk per thread and operand (TILE * CH > 256): the tile is
+// staged as NCH = 2 halves of RP = 16 rows.  A thread's second chunk is the same columns RP rows further down, so its address is
+// the first one's plus a wave-uniform RP * stride and the halves share every per-thread pointer; loads and stores stay branch-free
+// as in TilePair.  (A struct of its own, not a generalisation of TilePair: the instantiations up to head dim 64 keep the code
+// they had, instruction for instruction.)
+template <typename T, int HD>
+struct TilePairWide {
+  static constexpr int LD = Lds<HD, T>::LD;
+  static constexpr int CH = HD / 8;
+  static constexpr int NCH = (TILE * CH + ATT_THREADS - 1) / ATT_THREADS;   // chunks per thread and operand
+  static constexpr int RP = TILE / NCH;                                     // rows per half
+  static_assert(HD > 64 && NCH == 2 && RP * CH <= ATT_THREADS, "a half of a tile is at most one chunk per thread");
+  Frag<T> fa[NCH], fb[NCH];
+  int r, col;
+  bool has, ok[NCH];
+  const T* pa;   // this thread's chunk of the tile at position 0 of the sequence
+  const T* pb;
+  const T* za;   // this thread's chunk of a row that always exists: what a lane outside [lo, hi) fetches (and then zeroes)
+  const T* zb;
+  int64_t sa, sb;   // elements per position (wave-uniform)
+  __device__ __forceinline__ void init(const T* srcA, int64_t ldA, const T* srcB, int64_t ldB, int64_t row0, int64_t row_stride, int safe_pos) {
+    const int c = threadIdx.x;
+    has = c < RP * CH;
+    r = c / CH;
+    col = (c % CH) * 8;
+    pa = srcA + (row0 + (int64_t)r * row_stride) * ldA + col;
+    pb = srcB + (row0 + (int64_t)r * row_stride) * ldB + col;
+    za = srcA + (row0 + (int64_t)safe_pos * row_stride) * ldA + col;
+    zb = srcB + (row0 + (int64_t)safe_pos * row_stride) * ldB + col;
+    sa = row_stride * ldA;
+    sb = row_stride * ldB;
+#pragma unroll
+    for (int j = 0; j < NCH; ++j) ok[j] = false;
+  }
+  __device__ __forceinline__ void load(int pos0, int lo, int hi) {
+#pragma unroll
+    for (int j = 0; j < NCH; ++j) {
+      const int pos = pos0 + j * RP + r;
+      ok[j] = has && pos >= lo && pos < hi;
+      fa[j] = frag_load(ok[j] ? pa + (int64_t)(pos0 + j * RP) * sa : za);
+      fb[j] = frag_load(ok[j] ? pb + (int64_t)(pos0 + j * RP) * sb : zb);
+    }
+  }
+  template <typename TO, bool PIN = false>
+  __device__ __forceinline__ void store(typename TO::LT* sA, typename TO::LT* sB) const {
+    if constexpr (PIN) __builtin_amdgcn_sched_barrier(0);
+    if (has) {
+#pragma unroll
+      for (int j = 0; j < NCH; ++j) {
+        TO::store(sA, j * RP + r, col, ok[j] ? fa[j] : frag_zero<T>());
+        TO::store(sB, j * RP + r, col, ok[j] ? fb[j] : frag_zero<T>());
+      }
+    }
+  }
+};
+
+template <typename T, int HD>
+using Staging = typename std::conditional<(HD <= 64), TilePair<T, HD>, TilePairWide<T, HD>>::type;
 
 // What a kernel does with its LDS tiles and MFMA operands, by storage type T and arithmetic:
 //   plain (SP = false): tiles of T, operands Frag<T>, products by mma (bf16 MFMA; for fp32 rows the exact v_mfma_f32_16x16x4_f32 chains);
@@ -301,12 +365,12 @@ __global__ void __launch_bounds__(ATT_THREADS, 2) k_attn_fwd(AttnArgs a) {
   const uint32_t bh = (uint32_t)(seq * a.nhead + head);
   const uint32_t hq = rng_qpart(a.seed1, bh, (uint32_t)qp);
   const uint32_t thr16 = a.drop_thr << 16;
-  TilePair<T, HD> stg;
+  Staging<T, HD> stg;
   const T* srcK = qkv + a.d_model + head * HD;
   const T* srcV = qkv + 2 * a.d_model + head * HD;
   stg.init(srcK, ld3, srcV, ld3, row0, a.row_stride, kv_off < npos ? kv_off : npos - 1);
   const int k_first = (kv_off / TILE) * TILE;
-  if (HD < 32) __syncthreads();   // the zero fill above and the first store touch the same rows
+  if (Lds<HD, T>::PADDED) __syncthreads();   // the zero fill above and the first store touch the same rows
   stg.load(k_first, kv_off, kv_end);
   stg.template store<TO>(sKb[0], sVb[0]);
   __syncthreads();
@@ -466,12 +530,12 @@ __global__ void __launch_bounds__(ATT_THREADS, 2) k_attn_bwd_dq(AttnArgs a) {
   const int kv_end = kv_off + kv_len;
   const uint32_t bh = (uint32_t)(seq * a.nhead + head);
   const uint32_t hq = rng_qpart(a.seed1, bh, (uint32_t)qp);
-  TilePair<T, HD> stg;
+  Staging<T, HD> stg;
   const T* srcK = qkv + a.d_model + head * HD;
   const T* srcV = qkv + 2 * a.d_model + head * HD;
   stg.init(srcK, ld3, srcV, ld3, row0, a.row_stride, kv_off < npos ? kv_off : npos - 1);
   const int k_first = (kv_off / TILE) * TILE;
-  if (HD < 32) __syncthreads();
+  if (Lds<HD, T>::PADDED) __syncthreads();
   stg.load(k_first, kv_off, kv_end);
   stg.template store<TO>(sKb[0], sVb[0]);
   __syncthreads();
@@ -537,8 +601,14 @@ __global__ void __launch_bounds__(ATT_THREADS, 2) k_attn_bwd_dq(AttnArgs a) {
 // =================================================================================================
 // backward, pass 2: dK, dV                              (block = 64 keys, loop over query tiles)
 // =================================================================================================
+// Two blocks per CU is the register budget everywhere except the exact fp32 kernels above head dim 96: dk / dv (64 registers), the
+// K / V operands (64) and the two-chunk staging (32) leave too little of 256 for the step, and fp32 rows at these widths are the
+// parity mode -- one block per CU there instead of scratch.
+template <typename T, int HD, bool SP>
+constexpr int dkv_blocks_per_cu() { return (sizeof(T) == 4 && !SP && HD > 96) ? 1 : 2; }
+
 template <typename T, int HD, bool DENSE, bool SP = false>
-__global__ void __launch_bounds__(ATT_THREADS, 2) k_attn_bwd_dkv(AttnArgs a) {
+__global__ void __launch_bounds__(ATT_THREADS, (dkv_blocks_per_cu<T, HD, SP>())) k_attn_bwd_dkv(AttnArgs a) {
   using TO = TileOps<T, HD, SP>;
   using LT = typename TO::LT;
   using Op = typename TO::Op;
@@ -587,7 +657,7 @@ __global__ void __launch_bounds__(ATT_THREADS, 2) k_attn_bwd_dkv(AttnArgs a) {
   const uint32_t half_shift = (kp & 1) ? 0u : 16u;  // masked_fill masks are a separate instantiation: the common kernel carries none of it
   // a block whose 64 keys are all padding only writes zeros
   const bool any_valid = (k_base < kv_end) && (k_base + BLOCK_N > kv_off);
-  TilePair<T, HD> stg;
+  Staging<T, HD> stg;
   const T* srcQ = qkv + head * HD;
   const T* srcDO = dctx + head * HD;
   stg.init(srcQ, ld3, srcDO, a.d_model, row0, a.row_stride, 0);
@@ -612,7 +682,7 @@ __global__ void __launch_bounds__(ATT_THREADS, 2) k_attn_bwd_dkv(AttnArgs a) {
     return aux_ok ? v : 0.f;
   };
   const int q_begin = (a.q_last_only && npos > 0) ? ((npos - 1) / TILE) * TILE : 0;   // pooled mode: only the last position's gradient is non-zero
-  if (HD < 32) __syncthreads();
+  if (Lds<HD, T>::PADDED) __syncthreads();
   // (unconditional, also for a block whose keys are all padding: every path into the loop passes this store and with it the wait for
   // the bk / bv loads above -- behind `if (any_valid)` the wait-count pass kept them pending on the other path and put vmcnt(0) in
   // front of every step's first MFMA)
@@ -708,12 +778,15 @@ __global__ void __launch_bounds__(ATT_THREADS, 2) k_attn_bwd_dkv(AttnArgs a) {
   }
 }
 
+// the head dims with an instantiation: GT_HD_SWITCH below lists the same set
+bool head_dim_ok(int64_t hd) { return hd >= 8 && hd <= 128 && hd % 8 == 0; }
+
 int check_attn(const char* fn, int dtype, int64_t d_model, int nhead, int64_t num_seqs, int64_t max_npos,
                float dropout_p) {
   if (dtype != GT_F32 && dtype != GT_BF16) { gt_set_error("%s: bad dtype", fn); return GT_ERR_INVALID_ARG; }
   if (nhead <= 0 || d_model <= 0 || d_model % nhead != 0) { gt_set_error("%s: bad d_model/nhead", fn); return GT_ERR_INVALID_ARG; }
   int64_t hd = d_model / nhead;
-  if (hd != 8 && hd != 16 && hd != 32 && hd != 64) { gt_set_error("%s: head_dim %lld unsupported (8, 16, 32 or 64)", fn, (long long)hd); return GT_ERR_UNSUPPORTED; }
+  if (!head_dim_ok(hd)) { gt_set_error("%s: head_dim %lld unsupported (multiples of 8 from 8 to 128)", fn, (long long)hd); return GT_ERR_UNSUPPORTED; }
   if (num_seqs < 0 || num_seqs > 65535) { gt_set_error("%s: num_seqs out of range", fn); return GT_ERR_INVALID_ARG; }
   if (max_npos < 0) { gt_set_error("%s: bad max_npos", fn); return GT_ERR_INVALID_ARG; }
   if (!(dropout_p >= 0.f && dropout_p < 1.f)) { gt_set_error("%s: dropout_p must be in [0,1)", fn); return GT_ERR_INVALID_ARG; }
@@ -740,7 +813,24 @@ AttnArgs make_args(const void* qkv, const void* ctx, const void* d_ctx, float* l
 // yardstick (graphtrans_amd/w3.py sets it together with the exact fp32 GEMMs: GT_F32_GEMM=exact; tests/test_hip_options.py)
 bool attn_f32_split() { return !gt_opt(GT_OPT_ATTN_F32_EXACT); }
 
+// one exact instantiation per head dim (check_attn has let nothing else through)
+#define GT_HD_CASE(T, HD) case HD: GT_LAUNCH(T, HD); break;
+#define GT_HD_SWITCH(T)                                                                                  \
+  switch (hd) {                                                                                          \
+    GT_HD_CASE(T, 8) GT_HD_CASE(T, 16) GT_HD_CASE(T, 24) GT_HD_CASE(T, 32) GT_HD_CASE(T, 40) GT_HD_CASE(T, 48)       \
+    GT_HD_CASE(T, 56) GT_HD_CASE(T, 64) GT_HD_CASE(T, 72) GT_HD_CASE(T, 80) GT_HD_CASE(T, 88) GT_HD_CASE(T, 96)      \
+    GT_HD_CASE(T, 104) GT_HD_CASE(T, 112) GT_HD_CASE(T, 120) GT_HD_CASE(T, 128)                                      \
+    default: break;                                                                                      \
+  }
+
 }  // namespace
+
+// the predicate of check_attn, for a caller that would rather ask than provoke GT_ERR_UNSUPPORTED
+extern "C" int gt_attn_head_dim_ok(int dtype, int64_t d_model, int nhead) {
+  if (dtype != GT_F32 && dtype != GT_BF16) return 0;
+  if (nhead <= 0 || d_model <= 0 || d_model % nhead != 0) return 0;
+  return head_dim_ok(d_model / nhead) ? 1 : 0;
+}
 
 static int attn_fwd_impl(int pooled, int dtype, const void* qkv, void* ctx, float* lse, int64_t total_rows, int64_t d_model,
                            int nhead, const int32_t* seq_desc, int64_t num_seqs, int64_t row_stride,
@@ -771,12 +861,10 @@ static int attn_fwd_impl(int pooled, int dtype, const void* qkv, void* ctx, floa
   if (dtype == GT_F32 && !dense_launch && attn_f32_split() && (hd == 32 || hd == 64)) {   // bf16x6 products (TileOps<float, HD, true>)
     if (hd == 32) hipLaunchKernelGGL((k_attn_fwd<float, 32, false, true>), grid, dim3(ATT_THREADS), 0, stream, a);
     else hipLaunchKernelGGL((k_attn_fwd<float, 64, false, true>), grid, dim3(ATT_THREADS), 0, stream, a);
-  } else if (dtype == GT_F32) {
-    if (hd == 8) GT_LAUNCH(float, 8); else if (hd == 16) GT_LAUNCH(float, 16);
-    else if (hd == 32) GT_LAUNCH(float, 32); else GT_LAUNCH(float, 64);
+  } else if (dtype == GT_F32) {   // exact v_mfma_f32_16x16x4_f32 chains: every other head dim, dense masks, attn_f32_exact
+    GT_HD_SWITCH(float)
   } else {
-    if (hd == 8) GT_LAUNCH(gt_bf16, 8); else if (hd == 16) GT_LAUNCH(gt_bf16, 16);
-    else if (hd == 32) GT_LAUNCH(gt_bf16, 32); else GT_LAUNCH(gt_bf16, 64);
+    GT_HD_SWITCH(gt_bf16)
   }
 #undef GT_LAUNCH
   GT_CHECK_LAUNCH();
@@ -847,12 +935,10 @@ static int attn_bwd_impl(int pooled, int dtype, const void* qkv, const void* ctx
       hipLaunchKernelGGL((k_attn_bwd_dq<float, 64, false, true>), grid_q, dim3(ATT_THREADS), 0, stream, aq);
       hipLaunchKernelGGL((k_attn_bwd_dkv<float, 64, false, true>), grid, dim3(ATT_THREADS), 0, stream, a);
     }
-  } else if (dtype == GT_F32) {
-    if (hd == 8) GT_LAUNCH(float, 8); else if (hd == 16) GT_LAUNCH(float, 16);
-    else if (hd == 32) GT_LAUNCH(float, 32); else GT_LAUNCH(float, 64);
+  } else if (dtype == GT_F32) {   // exact v_mfma_f32_16x16x4_f32 chains: every other head dim, dense masks, attn_f32_exact
+    GT_HD_SWITCH(float)
   } else {
-    if (hd == 8) GT_LAUNCH(gt_bf16, 8); else if (hd == 16) GT_LAUNCH(gt_bf16, 16);
-    else if (hd == 32) GT_LAUNCH(gt_bf16, 32); else GT_LAUNCH(gt_bf16, 64);
+    GT_HD_SWITCH(gt_bf16)
   }
 #undef GT_LAUNCH
   GT_CHECK_LAUNCH();

@@ -818,6 +818,9 @@ def _eligible_static(model):
                     return False
         if enc.activation not in layers.ENC_ACT or enc.d_model % 8 or enc.compute_dtype not in (torch.float32, torch.bfloat16):
             return False
+        head_dim_ok = getattr(_lib.lib(), "gt_attn_head_dim_ok", None)   # (None: an A/B library of an earlier revision, GT_LIB_PATH)
+        if head_dim_ok is not None and not head_dim_ok(GT_F32, enc.d_model, enc.nhead):   # (the module path raises the library's own message)
+            return False
         for mod in enc.transformer.layers:
             if mod.linear1.weight.shape[0] % 8:
                 return False
@@ -875,6 +878,9 @@ def _eligible_static_pna(model):
         if model.gnn2transformer.in_features != c0.in_channels or c0.in_channels % 4 or c0.F_in % 4:
             return False
         if enc.activation not in layers.ENC_ACT or enc.d_model % 8 or enc.compute_dtype not in (torch.float32, torch.bfloat16):
+            return False
+        head_dim_ok = getattr(_lib.lib(), "gt_attn_head_dim_ok", None)   # (None: an A/B library of an earlier revision, GT_LIB_PATH)
+        if head_dim_ok is not None and not head_dim_ok(GT_F32, enc.d_model, enc.nhead):   # (the module path raises the library's own message)
             return False
         for mod in enc.transformer.layers:
             if mod.linear1.weight.shape[0] % 8:

@@ -306,7 +306,7 @@ int gt_seq_layout_packed(const int32_t* graph_ptr, int64_t B, int64_t max_input_
  * / dropout / bmm (modules/transformer_encoder.py:59) between in_proj and out_proj.
  *   qkv [rows][3*d_model] (torch packed in_proj order q|k|v), ctx [rows][d_model],
  *   lse [2][nhead][rows] fp32 (row max and log2 of the row sum, saved for backward).
- *   head_dim = d_model/nhead in {8, 16, 32, 64}.
+ *   head_dim = d_model/nhead: every multiple of 8 from 8 to 128 (ask gt_attn_head_dim_ok).
  *   Keys outside [kv_off, kv_off+kv_len) are masked (the key_padding_mask); every query position
  *   in [0, npos) is computed.  P = softmax(scale * q k^T); dropout(P, p) with a counter-based RNG
  *   keyed by (seed, seq, head, query, key) so backward replays it.
@@ -319,6 +319,9 @@ int gt_seq_layout_packed(const int32_t* graph_ptr, int64_t B, int64_t max_input_
  *   :44-47) — scores whose mask entry is 0 are FILLED with the finite `mask_value` (masked_fill
  *   semantics: a fully masked row becomes uniform, no gradient flows through a filled score).
  */
+/* 1 if gt_attn_fwd / gt_attn_bwd (and the _last forms) take this dtype and head_dim = d_model / nhead, else 0: the predicate their
+ * own argument check uses (anything else is GT_ERR_UNSUPPORTED there). */
+int gt_attn_head_dim_ok(int dtype, int64_t d_model, int nhead);
 int gt_attn_fwd(int dtype, const void* qkv, void* ctx, float* lse, int64_t total_rows, int64_t d_model, int nhead,
                 const int32_t* seq_desc, int64_t num_seqs, int64_t row_stride, int64_t max_npos,
                 const int32_t* work_items, int64_t num_work, const float* dense_mask, const float* key_valid,

@@ -61,7 +61,21 @@ def case(name, lens, d=128, nhead=4, dtype=torch.bfloat16, lpt=None, p=0.0):
     print(f"{name:34s} seqs {len(lens):4d} rows {lay.rows:6d} max {max(lens):5d}: fwd {t_f:7.1f} us ({fl / t_f / 1e6:6.1f} TF)  fwd+bwd {t_fb:7.1f} us")
 
 
+def wide_cases():
+    """d_model 512 as 8 heads of 64 and as 4 heads of 128: the same FLOPs and the same bytes, half as many scores per FLOP at 128"""
+    b = synth.code2_like(B=256, seed=1000)
+    n = list(np.minimum(torch.bincount(b.batch).numpy(), 1000) + 1)
+    for nhead in (8, 4):
+        hd = 512 // nhead
+        case(f"256 x 513 (ER), d512 hd{hd}", [513] * 256, d=512, nhead=nhead, lpt=True)
+        case(f"Code2-like batch, d512 hd{hd}", n, d=512, nhead=nhead, lpt=True)
+        case(f"Code2-like, dropout 0.3, d512 hd{hd}", n, d=512, nhead=nhead, lpt=True, p=0.3)
+
+
 if __name__ == "__main__":
+    if "--wide" in sys.argv:   # only the head-dim 64 / 128 pairs
+        wide_cases()
+        sys.exit(0)
     case("one sequence of 1001", [1001])
     case("one sequence of 513", [513])
     case("one sequence of 126", [126])
@@ -73,3 +87,4 @@ if __name__ == "__main__":
     case("Code2-like batch (seed 1000)", list(n))
     case("Code2-like batch, dropout 0.3", list(n), p=0.3)
     case("256 x 513 (ER), d256 h4", [513] * 256, d=256, nhead=4)
+    wide_cases()
