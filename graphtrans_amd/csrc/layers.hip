@@ -9,6 +9,7 @@
 //   GCN layer      modules/gnn_module.py:199-212 (vn add, conv, batch_norm, relu, residual) + modules/conv.py:50-71
 //   VN update      modules/gnn_module.py:217-229 (global_add_pool + vn -> MLP)
 #include "gt_common.h"
+#include "linear_call.h"
 
 namespace {
 
@@ -280,6 +281,17 @@ extern "C" int gt_encoder_layer_fwd(const gt_encoder_layer* L, const void* x, vo
   return GT_OK;
 }
 
+// linear2's backward over `rows` token rows with the gate of f1 (ReLU + dropout: the forward output; GELU: the saved multiplier g1) on
+// its dX OUTPUT d_f1 (gt_linear_bwd_gate_out's call, as a record)
+static int enc_linear2_bwd(const gt_encoder_layer* L, const void* f1, const void* g1, const void* d_f2, void* d_f1, float* dw, float* db,
+                           int64_t rows, int c, float p, void* ws, size_t ws_bytes, gt_stream_t st) {
+  LinBwd lin{L->dtype, L->dtype, c, f1, L->l2_w, d_f2, L->act == 1 ? g1 : f1, nullptr, nullptr, d_f1, dw, db, rows, L->d_model, L->ffn,
+               L->ffn, L->d_model, 1, 0, 0, L->act == 1 ? 0.f : p, ws, ws_bytes, (hipStream_t)st};
+  lin.gate_out = true;
+  lin.mul_mask = L->act == 1;
+  return lin_bwd(lin);
+}
+
 extern "C" int gt_encoder_layer_bwd(const gt_encoder_layer* L, const void* x, const void* dy, const void* saved, void* dx,
                                     float* grads, void* workspace, size_t workspace_bytes, gt_stream_t st) {
   GT_TRY(enc_check("gt_encoder_layer_bwd", L));
@@ -301,8 +313,7 @@ extern "C" int gt_encoder_layer_bwd(const gt_encoder_layer* L, const void* x, co
   if (gt_linear_bwd_gate_out_ok(t, t, c, L->l2_w, R, d, F)) {
     // weight-stationary path (linear1.h): linear2's dX GEMM writes the GATED gradient dZ1 = (dF2 W2) * act'(.) * dropout scale, the
     // tensor both GEMMs of linear1's backward read (the tiled kernels gate d_f1 while they stage it, twice)
-    GT_TRY(gt_linear_bwd_gate_out(t, t, c, s.f1, L->l2_w, w.d_f2, L->act == 1 ? s.g1 : s.f1, nullptr, nullptr, w.d_f1, g.l2_w, g.l2_b, R, d, F,
-                                  F, d, L->act == 1 ? -1.f : p, w.lin_ws, w.lin_ws_bytes, st));
+    GT_TRY(enc_linear2_bwd(L, s.f1, s.g1, w.d_f2, w.d_f1, g.l2_w, g.l2_b, R, c, p, w.lin_ws, w.lin_ws_bytes, st));
     if (gt_linear_bwd_dx_layernorm_ok(t, c, L->l1_w, R, F, d) && w.ln_ws_bytes >= gt_linear_bwd_dx_layernorm_workspace_bytes(R, F, d)) {
       // linear1's dX GEMM ends in norm1's backward (x1 = LN1(x + drop(a))): d_x1 + dZ1 W1 never reaches memory (linear1.h, LNB epilogue)
       // (the weight gradient is forked BEHIND the dX launch, as gt_linear_bwd does: beside it, it slowed the critical kernel)
@@ -474,15 +485,16 @@ extern "C" int gt_gcn_layer_bwd(const gt_gcn_layer* L, const void* x, const void
                           L->table_rows, nullptr, w.d_lin, g.root, g.edge_w, g.edge_b, nullptr, w.agg_ws, w.agg_ws_bytes, st));
   // d_x = d_lin W (+ grads reaching x from its other consumers) (+ dy through the residual branch)
   if (L->ev_dx_wait) GT_TRY(gt_stream_wait_event(st, L->ev_dx_wait));
+  LinBwd lin{GT_F32, GT_F32, L->compute, x, L->lin_w, w.d_lin, nullptr, dx_extra, L->residual ? dy : nullptr, d_h_in, g.lin_w, g.lin_b,
+               L->N, L->D, L->D, L->D, L->D, 1, 0, 0, 0.f, w.lin_ws, w.lin_ws_bytes, (hipStream_t)st};
+  lin.weight_t = L->lin_wt;
   if (L->prev_saved && L->prev_bn_part) {   // d_h_in is the dy of the previous layer's BatchNorm: its statistics ride in this epilogue
     const GcnSaved ps = gcn_saved(L, const_cast<void*>(L->prev_saved));
-    GT_TRY(gt_linear_bwd_bnstats((const float*)ps.agg, L->D, ps.stats, ps.stats + L->D, L->prev_bn_w, L->prev_bn_b, L->prev_relu,
-                                 L->prev_bn_part));
+    lin.bn_x = (const float*)ps.agg; lin.bn_ldx = L->D; lin.bn_mean = ps.stats; lin.bn_rstd = ps.stats + L->D;
+    lin.bn_w = L->prev_bn_w; lin.bn_b = L->prev_bn_b; lin.bn_relu = L->prev_relu; lin.bn_part = L->prev_bn_part;
   }
-  // (the broadcast request is consumed -- or dropped -- by the very next gt_linear_bwd* call of this thread: this one)
-  if (L->dx_bcast) GT_TRY(gt_linear_bwd_bcast(L->dx_bcast, L->dx_bcast_idx));
-  GT_TRY(gt_linear_bwd_wt(GT_F32, GT_F32, L->compute, x, L->lin_w, L->lin_wt, w.d_lin, nullptr, dx_extra, L->residual ? dy : nullptr,
-                          d_h_in, g.lin_w, g.lin_b, L->N, L->D, L->D, 0.f, w.lin_ws, w.lin_ws_bytes, st));
+  lin.bcast = L->dx_bcast; lin.bcast_idx = L->dx_bcast_idx;
+  GT_TRY(lin_bwd(lin));
   if (L->has_vn && d_vn)
     GT_TRY(gt_segment_sum_ws(GT_F32, d_h_in, nullptr, L->graph_ptr, L->N, L->B, L->D, d_vn, w.seg_ws, w.seg_ws_bytes, st));
   return GT_OK;
@@ -613,12 +625,16 @@ extern "C" int gt_gin_layer_bwd(const gt_gin_layer* L, const void* x, const void
   const int64_t N = L->N, D = L->D;
   GT_TRY(gt_batchnorm_bwd(GT_F32, s.z2, dy, L->bn_w, L->bn_b, s.st, s.st + D, L->training, L->relu, N, D, w.d_z2, g.bn_w, g.bn_b,
                           L->dropout_p, L->seed, w.bn_ws, w.bn_ws_bytes, st));
-  GT_TRY(gt_linear_bwd_wt(GT_F32, GT_F32, L->compute, s.a1, L->w2, L->w2_t, w.d_z2, nullptr, nullptr, nullptr, w.d_a1, g.w2, g.b2, N, D,
-                          2 * D, 0.f, w.lin_ws, w.lin_ws_bytes, st));
+  LinBwd lin{GT_F32, GT_F32, L->compute, s.a1, L->w2, w.d_z2, nullptr, nullptr, nullptr, w.d_a1, g.w2, g.b2, N, D, 2 * D, 2 * D, D, 1, 0, 0,
+               0.f, w.lin_ws, w.lin_ws_bytes, (hipStream_t)st};
+  lin.weight_t = L->w2_t;
+  GT_TRY(lin_bwd(lin));
   GT_TRY(gt_batchnorm_bwd(GT_F32, s.z1, w.d_a1, L->bn1_w, L->bn1_b, s.st1, s.st1 + 2 * D, L->training, 1, N, 2 * D, w.d_z1,
                           g.bn1_w, g.bn1_b, 0.f, 0, w.bn_ws, w.bn_ws_bytes, st));
-  GT_TRY(gt_linear_bwd_wt(GT_F32, GT_F32, L->compute, s.agg, L->w1, L->w1_t, w.d_z1, nullptr, nullptr, nullptr, w.d_agg, g.w1, g.b1, N,
-                          2 * D, D, 0.f, w.lin_ws1, w.lin_ws_bytes, st));
+  lin = LinBwd{GT_F32, GT_F32, L->compute, s.agg, L->w1, w.d_z1, nullptr, nullptr, nullptr, w.d_agg, g.w1, g.b1, N, 2 * D, D, D, 2 * D, 1, 0, 0,
+               0.f, w.lin_ws1, w.lin_ws_bytes, (hipStream_t)st};
+  lin.weight_t = L->w1_t;
+  GT_TRY(lin_bwd(lin));
   const bool adds = dx_extra || L->residual;
   void* dx_conv = adds ? w.d_x : d_h_in;
   GT_TRY(gt_aggregate_bwd(GT_CONV_GIN, L->edge_mode, GT_F32, x, w.d_agg, N, L->E, D, L->out_ptr, L->out_dst, L->out_eid, nullptr,
@@ -759,8 +775,7 @@ extern "C" int gt_encoder_layer_pooled_bwd(const gt_encoder_layer* L, const void
   GT_TRY(gt_layernorm_bwd(t, s.f2, s.x1, dy_pool, L->n2_w, s.st2, s.st2 + B, p, L->seed ^ 0x14057B7EF767814FULL, B, d, w.d_f2, w.d_x1, g.n2_w,
                           g.n2_b, w.ln_ws, w.ln_ws_bytes, st));
   if (gt_linear_bwd_gate_out_ok(t, t, c, L->l2_w, B, d, F)) {
-    GT_TRY(gt_linear_bwd_gate_out(t, t, c, s.f1, L->l2_w, w.d_f2, L->act == 1 ? s.g1 : s.f1, nullptr, nullptr, w.d_f1, g.l2_w, g.l2_b, B, d, F,
-                                  F, d, L->act == 1 ? -1.f : p, w.lin_ws, w.lin_ws_bytes, st));
+    GT_TRY(enc_linear2_bwd(L, s.f1, s.g1, w.d_f2, w.d_f1, g.l2_w, g.l2_b, B, c, p, w.lin_ws, w.lin_ws_bytes, st));
     GT_TRY(gt_linear_bwd(t, t, c, s.x1, L->l1_w, w.d_f1, nullptr, w.d_x1, nullptr, w.d_x1, g.l1_w, g.l1_b, B, F, d, 0.f, w.lin_ws,
                          w.lin_ws_bytes, st));
   } else {

@@ -19,6 +19,7 @@
 #include <mutex>
 
 #include "gt_common.h"
+#include "linear_call.h"
 #include "mfma_frag.h"
 
 namespace {
@@ -893,204 +894,200 @@ void w32_launch_dw_nt(int nt, dim3 grid, hipStream_t stream, const L32DwArgs& a)
   }
 }
 
+
+// ---- per-call requests of the outside ABI -----------------------------------------------------------------------------------------
+// gt_linear_set_rows, gt_linear_set_rows_layernorm, gt_linear_bwd_bnstats and gt_linear_bwd_bcast have no call of their own: what they
+// ask for waits here, per host thread, for the next public gt_linear_fwd* / gt_linear_bwd* call, which moves it into its record
+// (take_map / take_bwd: the only readers) -- only the request fields of this record are ever set.  The dispatchers below and the
+// library's own layers never see it: they pass records.
+thread_local LinBwd g_pending{};
+// a forward call takes the row map, whatever its outcome, and leaves the backward's requests in place
+LinRowMap take_map() {
+  const LinRowMap m = g_pending.map;
+  g_pending.map = LinRowMap{};
+  return m;
+}
+// a backward call takes everything, whatever its outcome
+void take_bwd(LinBwd& c) {
+  const LinBwd& p = g_pending;
+  c.map = p.map; c.bcast = p.bcast; c.bcast_idx = p.bcast_idx;
+  c.bn_x = p.bn_x; c.bn_mean = p.bn_mean; c.bn_rstd = p.bn_rstd; c.bn_w = p.bn_w; c.bn_b = p.bn_b; c.bn_part = p.bn_part; c.bn_ldx = p.bn_ldx; c.bn_relu = p.bn_relu;
+  g_pending = LinBwd{};
+}
+// errors raised inside the dispatchers keep the texts of the entry points they were split from
+#define LIN_CHECK_ARG(fn, cond, msg) \
+  do { if (!(cond)) { gt_set_error("%s: %s", fn, msg); return GT_ERR_INVALID_ARG; } } while (0)
+#define LIN_DIMS(c) {(c).M, (c).N, (c).K, (c).x_dtype, (c).y_dtype, (c).compute}
+
+// what the forward and the backward check alike (fn, what: the names their errors carry; min_ldx: K, or the split under cat2, whose first
+// matrix holds columns [0, split))
+int check_call(const char* fn, const char* what, int x_dtype, int y_dtype, int compute, int64_t M, int64_t N, int64_t K, int64_t ldx, int64_t ldy,
+               int64_t min_ldx, int groups, int64_t x_group_stride, int64_t y_group_stride) {
+  LIN_CHECK_ARG(fn, groups >= 1 && groups <= 65535, "1..65535 groups");
+  LIN_CHECK_ARG(fn, groups == 1 || (x_group_stride % (x_dtype == GT_BF16 ? 8 : 4) == 0 && y_group_stride % (y_dtype == GT_BF16 ? 8 : 4) == 0 && (N * K) % 4 == 0),
+                "group strides must keep 16-byte alignment");
+  const int rc = check_lin(what, x_dtype, y_dtype, compute, M, N, K, ldy);
+  if (rc == GT_OK && (ldx < min_ldx || ldx % (x_dtype == GT_BF16 ? 8 : 4))) {
+    gt_set_error("%s: ldx (%lld) must be >= K and a multiple of 16 bytes", what, (long long)ldx);
+    return GT_ERR_UNSUPPORTED;
+  }
+  return rc;
+}
+bool rows_eligible(int compute, int x_dtype, int y_dtype, const float* weight, int64_t M, int64_t N, int64_t K) {
+  return w32_eligible(compute, x_dtype, M, 1) && (y_dtype == GT_F32 || N % 8 == 0) && w3_lookup(weight, N, K, false) && w3_lookup(weight, N, K, true);
+}
+
+// ---- forward: one function per kernel family, in order of preference --------------------------------------------------------------
+// Each either declines (false) or takes the call (true): it enqueues its launch, or sets rc to the error it met.
+bool fwd_heads(const LinFwd& f, const LinArgs& a, int&) {   // the prediction heads (linear_heads.h)
+  if (!heads_shape_ok(f.x_dtype, f.y_dtype, f.M, f.N, f.K, f.ldx, f.ldy, f.groups) || f.act != 0 || a.thr || f.gout) return false;
+  hipStream_t stream = f.stream;
+  HeadsArgs h{};
+  h.x = (const float*)f.x; h.w = f.weight; h.bias = f.bias; h.out = (float*)f.y; h.M = f.M; h.N = f.N; h.ldx = f.ldx; h.ldy = f.ldy;
+  GtProfScope pk__(GT_PROF_GEMM_KERNEL, "k_heads_fwd", stream, LIN_DIMS(f));
+  heads_launch_fwd(f.compute, stream, h);
+  return true;
+}
+bool fwd_small(const LinFwd& f, const LinArgs& a, int&) {   // short M (linear_small.h), wide outputs included
+  if (!small_eligible(f.x_dtype, f.y_dtype, f.M, f.N, f.K, f.ldx, f.ldy, f.groups) && !small_wide_ok(f.x_dtype, f.y_dtype, f.M, f.K, f.ldx, f.ldy, f.groups))
+    return false;
+  hipStream_t stream = f.stream;
+  SmallArgs sa{};
+  sa.x = (const float*)f.x; sa.w = f.weight; sa.bias = f.bias; sa.out = (float*)f.y; sa.M = f.M; sa.N = f.N; sa.K = f.K; sa.ldx = f.ldx; sa.ldy = f.ldy;
+  sa.act = f.act; sa.gout = (float*)f.gout; sa.inv_keep = a.inv_keep; sa.thr = a.thr; sa.s0 = a.s0; sa.s1 = a.s1;
+  GtProfScope pk__(GT_PROF_GEMM_KERNEL, "k_small_fwd", stream, LIN_DIMS(f));
+  small_launch(SMALL_FWD, f.compute, gt_cdiv(f.M, 16) * gt_cdiv(f.N, 32), f.K, stream, sa);
+  return true;
+}
+// grouped big-M fp32 GEMMs whose group weights all have bound images (the towers of PNAConv): k_lin3 with blockIdx.y = group
+bool fwd_grouped3(const LinFwd& f, const LinArgs& a, int&) {
+  if (f.groups <= 1 || !g3_eligible(f.compute, f.x_dtype, f.y_dtype, f.M, f.N, f.K, f.ldx, f.ldy) || f.act == 2 || f.x2) return false;
+  int64_t spacing = 0;
+  const void* img = w3_lookup_grouped(f.weight, f.N, f.K, f.groups, false, &spacing);
+  if (!img) return false;
+  hipStream_t stream = f.stream;
+  L32Args w{};
+  w.a = f.x; w.bias = f.bias; w.out = f.y; w.M = f.M; w.Nout = f.N; w.Kc = f.K; w.lda = f.ldx; w.ldw = f.K; w.ldo = f.ldy;
+  w.act = f.act; w.inv_keep = a.inv_keep; w.thr = a.thr; w.s0 = a.s0; w.s1 = a.s1;
+  w.w3 = img; w.groups = f.groups; w.g_a = f.x_group_stride; w.g_o = f.y_group_stride; w.g_img = spacing; w.g_b = (int)f.N;
+  GtProfScope pk__(GT_PROF_GEMM_KERNEL, "k_lin3[fwd]", stream, LIN_DIMS(f));
+  w3_launch<false>(f.x_dtype, f.y_dtype, stream, w);
+  return true;
+}
+// big-M exact-fp32 compute: the bf16x6 kernels on a bound image of the weight (k_lin3r / k_lin3), else the exact-fp32 MFMA kernel (k_lin32)
+bool fwd_wide(const LinFwd& f, const LinArgs& a, int& rc) {
+  if (!w32_eligible(f.compute, f.x_dtype, f.M, f.groups) || (f.act == 2 && (f.x_dtype != GT_F32 || f.y_dtype != GT_F32))) return false;
+  hipStream_t stream = f.stream;
+  const auto fail = [&rc](const char* msg) { gt_set_error("%s", msg); rc = GT_ERR_UNSUPPORTED; return true; };
+  L32Args w{};
+  w.a = f.x; w.w = f.weight; w.bias = f.bias; w.out = f.y; w.M = f.M; w.Nout = f.N; w.Kc = f.K; w.lda = f.ldx; w.ldw = f.K; w.ldo = f.ldy;
+  w.act = f.act; w.gout = f.gout; w.inv_keep = a.inv_keep; w.thr = a.thr; w.s0 = a.s0; w.s1 = a.s1;
+  // a prepared bf16x3 image of this weight (gt_w3_bind): the fp32-accurate GEMM on the bf16 matrix pipe (linear3x.h);
+  // bf16 rows need K % 8 (their 16-byte chunks are whole k-groups)
+  w.w3 = (f.x_dtype == GT_F32 || f.K % 8 == 0) ? w3_lookup(f.weight, f.N, f.K, false) : nullptr;
+  if (f.x2) {
+    if (!w.w3 || f.x_dtype != GT_F32) return fail("gt_linear_fwd_cat2: needs a bound weight image and fp32 rows");
+    w.a2 = f.x2; w.a_split = f.x_split; w.lda2 = f.ldx2;
+  }
+  if (f.map.rows) {
+    if (!w.w3) return fail("gt_linear_set_rows: needs a bound weight image");
+    w.out_rows = f.map.rows;
+    if (f.map.ln_out) {
+      if (w3_pick_nt(f.N) * 16 != f.N || f.act != 0 || a.thr || f.ldy != f.N)
+        return fail("gt_linear_set_rows_layernorm: the row must fill one column block (ask gt_linear_rows_layernorm_ok)");
+      w.ln_w = f.map.ln_w; w.ln_b = f.map.ln_b; w.ln_out = f.map.ln_out; w.ln_mean = f.map.ln_mean; w.ln_rstd = f.map.ln_rstd;
+      w.ln_eps = f.map.ln_eps;
+    }
+  }
+  const bool on_rows_kernel = w.w3 && w3r_ok(f.x_dtype, f.y_dtype, w);
+  GtProfScope pk__(GT_PROF_GEMM_KERNEL, on_rows_kernel ? "k_lin3r[fwd]" : (w.w3 ? "k_lin3[fwd]" : "k_lin32[fwd]"), stream, LIN_DIMS(f));
+  if (on_rows_kernel) w3r_launch(stream, w);   // rows straight into fragments (linear3r.h)
+  else if (w.w3) w3_launch<false>(f.x_dtype, f.y_dtype, stream, w);
+  else w32_launch<false>(f.x_dtype, f.y_dtype, stream, w);
+  return true;
+}
+// bf16 rows in and out with a bound fragment-order image of this weight (gt_w1_bind): the weight-stationary kernel (linear1.h)
+bool fwd_bf16_image(const LinFwd& f, const LinArgs& a, int&) {
+  if (f.x_dtype != GT_BF16 || f.y_dtype != GT_BF16 || f.compute != GT_BF16 || f.groups != 1 || f.act == 2 || f.M < W1_MIN_M) return false;
+  const void* img = w1_lookup(f.weight, f.N, f.K, false);
+  if (!img) return false;
+  hipStream_t stream = f.stream;
+  L1Args l{};
+  l.a = (const gt_bf16*)f.x; l.img = (const unsigned char*)img; l.bias = f.bias; l.out = (gt_bf16*)f.y;
+  l.M = f.M; l.lda = f.ldx; l.ldo = f.ldy; l.N = (int)f.N; l.K = (int)f.K; l.act = f.act;
+  l.inv_keep = a.inv_keep; l.thr = a.thr; l.s0 = a.s0; l.s1 = a.s1;
+  // many rows, or a contraction the registers cannot hold: both operands through the LDS ring (linear2.h)
+  const bool ring = w2_take(l, w1_pick_ntw(f.N, f.K) != 0);
+  GtProfScope pk__(GT_PROF_GEMM_KERNEL, ring ? "k_lin2[fwd]" : "k_lin1[fwd]", stream, LIN_DIMS(f));
+  return ring ? w2_launch(stream, l) : w1_launch(stream, l);   // (false: no launch, the tiled kernel runs it)
+}
+void fwd_tiled(const LinFwd& f, LinArgs a) {
+  hipStream_t stream = f.stream;
+  const int compute = f.compute, bm = pick_bm(f.M, f.K, true);
+  a.ntiles = (int)gt_cdiv(f.N, BN);
+  dim3 grid((unsigned)(gt_cdiv(gt_cdiv(f.M, bm), 8) * 8 * a.ntiles), (unsigned)f.groups);
+  const int t0 = f.x_dtype, t1 = f.y_dtype;
+  GtProfScope pk__(GT_PROF_GEMM_KERNEL, "k_linear_fwd", stream, LIN_DIMS(f));
+  if (bm == 64) GT_LIN_DISPATCH_BM(k_linear_fwd, 64, grid, a);
+  else GT_LIN_DISPATCH_BM(k_linear_fwd, 128, grid, a);
+}
 }  // namespace
 
-extern "C" int gt_linear_fwd(int x_dtype, int y_dtype, int compute, const void* x, const float* weight,
-                             const float* bias, void* y, int64_t M, int64_t N, int64_t K, int act, float dropout_p,
-                             uint64_t seed, gt_stream_t stream_) {
-  return gt_linear_fwd_ld(x_dtype, y_dtype, compute, x, weight, bias, y, M, N, K, N, act, dropout_p, seed, stream_);
+int lin_fwd(const LinFwd& f) {
+  const char* fn = "linear_fwd_impl";
+  LIN_CHECK_ARG(fn, !f.map.rows || (f.groups == 1 && rows_eligible(f.compute, f.x_dtype, f.y_dtype, f.weight, f.M, f.N, f.K)),
+                "gt_linear_set_rows: this GEMM does not take a row map (ask gt_linear_rows_ok)");
+  int rc = check_call(fn, "gt_linear_fwd", f.x_dtype, f.y_dtype, f.compute, f.M, f.N, f.K, f.ldx, f.ldy, f.x2 ? f.x_split : f.K, f.groups,
+                      f.x_group_stride, f.y_group_stride);
+  if (rc) return rc;
+  LIN_CHECK_ARG(fn, f.x && f.weight && f.y, "null buffer");
+  LIN_CHECK_ARG(fn, f.dropout_p >= 0.f && f.dropout_p < 1.f, "dropout_p must be in [0,1)");
+  if (f.M == 0) return GT_OK;
+  GtProfScope prof__(GT_PROF_LINEAR, "gt_linear_fwd", f.stream, LIN_DIMS(f));
+  LinArgs a{};
+  a.a = f.x; a.w = f.weight; a.bias = f.bias; a.out = f.y; a.M = f.M; a.N = f.N; a.K = f.K; a.ldy = f.ldy; a.ldx = f.ldx; a.act = f.act; a.gout = f.gout;
+  fill_drop(a, f.dropout_p, f.seed);
+  a.g_x = f.x_group_stride; a.g_y = f.y_group_stride; a.g_w = f.N * f.K; a.g_b = f.N;
+  if (!(fwd_heads(f, a, rc) || fwd_small(f, a, rc) || fwd_grouped3(f, a, rc) || fwd_wide(f, a, rc) || fwd_bf16_image(f, a, rc))) fwd_tiled(f, a);
+  if (rc) return rc;
+  hipError_t e = hipGetLastError();
+  if (e != hipSuccess) { gt_set_error("%s: launch failed: %s", fn, hipGetErrorString(e)); return GT_ERR_LAUNCH; }
+  return GT_OK;
 }
 
-extern "C" int gt_linear_fwd_ld(int x_dtype, int y_dtype, int compute, const void* x, const float* weight,
-                                const float* bias, void* y, int64_t M, int64_t N, int64_t K, int64_t ldy, int act,
-                                float dropout_p, uint64_t seed, gt_stream_t stream_) {
-  return gt_linear_fwd_ld2(x_dtype, y_dtype, compute, x, weight, bias, y, M, N, K, K, ldy, act, dropout_p, seed, stream_);
+extern "C" int gt_linear_fwd(int x_dtype, int y_dtype, int compute, const void* x, const float* weight, const float* bias, void* y, int64_t M,
+                             int64_t N, int64_t K, int act, float dropout_p, uint64_t seed, gt_stream_t stream_) {
+  return gt_linear_fwd_grouped(x_dtype, y_dtype, compute, x, weight, bias, y, M, N, K, K, N, 1, 0, 0, act, dropout_p, seed, stream_);
 }
 
-extern "C" int gt_linear_fwd_ld2(int x_dtype, int y_dtype, int compute, const void* x, const float* weight,
-                                 const float* bias, void* y, int64_t M, int64_t N, int64_t K, int64_t ldx, int64_t ldy,
-                                 int act, float dropout_p, uint64_t seed, gt_stream_t stream_) {
+extern "C" int gt_linear_fwd_ld(int x_dtype, int y_dtype, int compute, const void* x, const float* weight, const float* bias, void* y, int64_t M,
+                                int64_t N, int64_t K, int64_t ldy, int act, float dropout_p, uint64_t seed, gt_stream_t stream_) {
+  return gt_linear_fwd_grouped(x_dtype, y_dtype, compute, x, weight, bias, y, M, N, K, K, ldy, 1, 0, 0, act, dropout_p, seed, stream_);
+}
+
+extern "C" int gt_linear_fwd_ld2(int x_dtype, int y_dtype, int compute, const void* x, const float* weight, const float* bias, void* y, int64_t M,
+                                 int64_t N, int64_t K, int64_t ldx, int64_t ldy, int act, float dropout_p, uint64_t seed, gt_stream_t stream_) {
   return gt_linear_fwd_grouped(x_dtype, y_dtype, compute, x, weight, bias, y, M, N, K, ldx, ldy, 1, 0, 0, act, dropout_p, seed,
                                stream_);
 }
 
-static int linear_fwd_impl(int x_dtype, int y_dtype, int compute, const void* x, const float* weight, const float* bias, void* y,
-                           void* gout, int64_t M, int64_t N, int64_t K, int64_t ldx, int64_t ldy, int groups, int64_t x_group_stride,
-                           int64_t y_group_stride, int act, float dropout_p, uint64_t seed, gt_stream_t stream_);
-
-// The row operand / the dX of ONE call as two matrices side by side (the JK = "cat" concatenation without its copy): set by the
-// *_cat2 entry points for the duration of their call (per host thread), honoured by the bf16x6 path only.
-struct Cat2Req {
-  const void* x2 = nullptr;   // forward / dW: contraction columns [split, K) of X
-  void* dx2 = nullptr;        // dX: output columns [split, K)
-  int64_t split = 0, ld2 = 0;
-};
-thread_local Cat2Req g_cat2;
-struct Cat2Scope {
-  ~Cat2Scope() { g_cat2 = Cat2Req{}; }
-};
-
-// A row map for ONE call (gt_linear_set_rows; per host thread, consumed by the next gt_linear_fwd* / gt_linear_bwd* call whatever its
-// outcome): forward stores output row m at row rows[m] of y, backward reads row m of dY from row rows[m] of dy; -1 = no such row
-// (nothing stored / zeros read).  Honoured by the bf16x6 path only: gt_linear_rows_ok.
-thread_local const int32_t* g_rows = nullptr;
-struct RowsLn {   // + a LayerNorm of the stored output row in the forward's epilogue (gt_linear_set_rows_layernorm)
-  const float *w = nullptr, *b = nullptr;
-  void* out = nullptr;
-  float *mean = nullptr, *rstd = nullptr;
-  float eps = 0.f;
-};
-thread_local RowsLn g_rows_ln;
-struct RowsTake {   // takes the request out of the thread state on entry: it can never leak into a later call
-  const int32_t* rows;
-  RowsLn ln;
-  RowsTake() : rows(g_rows), ln(g_rows_ln) { g_rows = nullptr; g_rows_ln = RowsLn{}; }
-};
-struct RowsClear {   // for entry points that can fail in front of the call that takes the request
-  ~RowsClear() { g_rows = nullptr; g_rows_ln = RowsLn{}; }
-};
-static inline bool rows_eligible(int compute, int x_dtype, int y_dtype, const float* weight, int64_t M, int64_t N, int64_t K) {
-  return w32_eligible(compute, x_dtype, M, 1) && (y_dtype == GT_F32 || N % 8 == 0) && w3_lookup(weight, N, K, false) && w3_lookup(weight, N, K, true);
-}
-
-extern "C" int gt_linear_fwd_grouped(int x_dtype, int y_dtype, int compute, const void* x, const float* weight,
-                                     const float* bias, void* y, int64_t M, int64_t N, int64_t K, int64_t ldx, int64_t ldy,
-                                     int groups, int64_t x_group_stride, int64_t y_group_stride, int act, float dropout_p,
-                                     uint64_t seed, gt_stream_t stream_) {
+extern "C" int gt_linear_fwd_grouped(int x_dtype, int y_dtype, int compute, const void* x, const float* weight, const float* bias, void* y, int64_t M,
+                                     int64_t N, int64_t K, int64_t ldx, int64_t ldy, int groups, int64_t x_group_stride, int64_t y_group_stride,
+                                     int act, float dropout_p, uint64_t seed, gt_stream_t stream_) {
   GT_CHECK_ARG(act == 0 || act == 1, "act must be 0 (none) or 1 (relu); gelu: gt_linear_fwd_gelu");
   GT_CHECK_ARG(dropout_p == 0.f || act == 1, "fused dropout requires a fused activation");
-  return linear_fwd_impl(x_dtype, y_dtype, compute, x, weight, bias, y, nullptr, M, N, K, ldx, ldy, groups, x_group_stride,
-                         y_group_stride, act, dropout_p, seed, stream_);
+  LinFwd f{x_dtype, y_dtype, compute, x, weight, bias, y, M, N, K, ldx, ldy, groups, x_group_stride, y_group_stride, act, dropout_p, seed, (hipStream_t)stream_};
+  f.map = take_map();
+  return lin_fwd(f);
 }
 
-// Y = dropout(gelu(X W^T + b)); gmul (nullable, storage type / pitch of Y) = gelu'(z) * dropout scale: the multiplier
-// gt_linear_bwd_mul takes in place of the ReLU path's forward output
-extern "C" int gt_linear_fwd_gelu(int x_dtype, int y_dtype, int compute, const void* x, const float* weight, const float* bias,
-                                  void* y, void* gmul, int64_t M, int64_t N, int64_t K, int64_t ldx, int64_t ldy, float dropout_p,
-                                  uint64_t seed, gt_stream_t stream_) {
-  return linear_fwd_impl(x_dtype, y_dtype, compute, x, weight, bias, y, gmul, M, N, K, ldx, ldy, 1, 0, 0, 2, dropout_p, seed, stream_);
-}
-
-static int linear_fwd_impl(int x_dtype, int y_dtype, int compute, const void* x, const float* weight, const float* bias, void* y,
-                           void* gout, int64_t M, int64_t N, int64_t K, int64_t ldx, int64_t ldy, int groups, int64_t x_group_stride,
-                           int64_t y_group_stride, int act, float dropout_p, uint64_t seed, gt_stream_t stream_) {
-  const RowsTake rows__;
-  GT_CHECK_ARG(!rows__.rows || (groups == 1 && rows_eligible(compute, x_dtype, y_dtype, weight, M, N, K)),
-               "gt_linear_set_rows: this GEMM does not take a row map (ask gt_linear_rows_ok)");
-  GT_CHECK_ARG(groups >= 1 && groups <= 65535, "1..65535 groups");
-  GT_CHECK_ARG(groups == 1 || (x_group_stride % (x_dtype == GT_BF16 ? 8 : 4) == 0 && y_group_stride % (y_dtype == GT_BF16 ? 8 : 4) == 0 &&
-                               (N * K) % 4 == 0),
-               "group strides must keep 16-byte alignment");
-  int rc = check_lin("gt_linear_fwd", x_dtype, y_dtype, compute, M, N, K, ldy);
-  if (rc == GT_OK && (ldx < (g_cat2.x2 ? g_cat2.split : K) || ldx % (x_dtype == GT_BF16 ? 8 : 4))) {   // (cat2: the first matrix holds columns [0, split))
-    gt_set_error("gt_linear_fwd: ldx (%lld) must be >= K and a multiple of 16 bytes", (long long)ldx);
-    rc = GT_ERR_UNSUPPORTED;
-  }
-  if (rc) return rc;
-  GT_CHECK_ARG(x && weight && y, "null buffer");
-  GT_CHECK_ARG(dropout_p >= 0.f && dropout_p < 1.f, "dropout_p must be in [0,1)");
-  if (M == 0) return GT_OK;
-  GtProfScope prof__(GT_PROF_LINEAR, "gt_linear_fwd", stream_, {M, N, K, x_dtype, y_dtype, compute});
-  hipStream_t stream = (hipStream_t)stream_;
-  LinArgs a{};
-  a.a = x; a.w = weight; a.bias = bias; a.out = y; a.M = M; a.N = N; a.K = K; a.ldy = ldy; a.ldx = ldx; a.act = act; a.gout = gout;
-  fill_drop(a, dropout_p, seed);
-  a.g_x = x_group_stride; a.g_y = y_group_stride; a.g_w = N * K; a.g_b = N;
-  if (heads_shape_ok(x_dtype, y_dtype, M, N, K, ldx, ldy, groups) && act == 0 && !a.thr && !gout) {   // the prediction heads (linear_heads.h)
-    HeadsArgs h{};
-    h.x = (const float*)x; h.w = weight; h.bias = bias; h.out = (float*)y; h.M = M; h.N = N; h.ldx = ldx; h.ldy = ldy;
-    {
-      GtProfScope pk__(GT_PROF_GEMM_KERNEL, "k_heads_fwd", stream, {M, N, K, x_dtype, y_dtype, compute});
-      heads_launch_fwd(compute, stream, h);
-    }
-    GT_CHECK_LAUNCH();
-    return GT_OK;
-  }
-  if (small_eligible(x_dtype, y_dtype, M, N, K, ldx, ldy, groups) || small_wide_ok(x_dtype, y_dtype, M, K, ldx, ldy, groups)) {
-    SmallArgs sa{};
-    sa.x = (const float*)x; sa.w = weight; sa.bias = bias; sa.out = (float*)y; sa.M = M; sa.N = N; sa.K = K; sa.ldx = ldx; sa.ldy = ldy;
-    sa.act = act; sa.gout = (float*)gout; sa.inv_keep = a.inv_keep; sa.thr = a.thr; sa.s0 = a.s0; sa.s1 = a.s1;
-    {
-      GtProfScope pk__(GT_PROF_GEMM_KERNEL, "k_small_fwd", stream, {M, N, K, x_dtype, y_dtype, compute});
-      small_launch(SMALL_FWD, compute, gt_cdiv(M, 16) * gt_cdiv(N, 32), K, stream, sa);
-    }
-    GT_CHECK_LAUNCH();
-    return GT_OK;
-  }
-  if (groups > 1 && g3_eligible(compute, x_dtype, y_dtype, M, N, K, ldx, ldy) && act != 2 && !g_cat2.x2) {
-    // grouped big-M fp32 GEMMs whose group weights all have bound images (the towers of PNAConv): k_lin3 with blockIdx.y = group
-    int64_t spacing = 0;
-    if (const void* img = w3_lookup_grouped(weight, N, K, groups, false, &spacing)) {
-      L32Args w{};
-      w.a = x; w.bias = bias; w.out = y; w.M = M; w.Nout = N; w.Kc = K; w.lda = ldx; w.ldw = K; w.ldo = ldy;
-      w.act = act; w.inv_keep = a.inv_keep; w.thr = a.thr; w.s0 = a.s0; w.s1 = a.s1;
-      w.w3 = img; w.groups = groups; w.g_a = x_group_stride; w.g_o = y_group_stride; w.g_img = spacing; w.g_b = (int)N;
-      {
-        GtProfScope pk__(GT_PROF_GEMM_KERNEL, "k_lin3[fwd]", stream, {M, N, K, x_dtype, y_dtype, compute});
-        w3_launch<false>(x_dtype, y_dtype, stream, w);
-      }
-      GT_CHECK_LAUNCH();
-      return GT_OK;
-    }
-  }
-  if (w32_eligible(compute, x_dtype, M, groups) && (act != 2 || (x_dtype == GT_F32 && y_dtype == GT_F32))) {
-    L32Args w{};
-    w.a = x; w.w = weight; w.bias = bias; w.out = y; w.M = M; w.Nout = N; w.Kc = K; w.lda = ldx; w.ldw = K; w.ldo = ldy;
-    w.act = act; w.gout = gout; w.inv_keep = a.inv_keep; w.thr = a.thr; w.s0 = a.s0; w.s1 = a.s1;
-    // a prepared bf16x3 image of this weight (gt_w3_bind): the fp32-accurate GEMM on the bf16 matrix pipe (linear3x.h);
-    // bf16 rows need K % 8 (their 16-byte chunks are whole k-groups)
-    w.w3 = (x_dtype == GT_F32 || K % 8 == 0) ? w3_lookup(weight, N, K, false) : nullptr;
-    if (g_cat2.x2) {
-      if (!w.w3 || x_dtype != GT_F32) { gt_set_error("gt_linear_fwd_cat2: needs a bound weight image and fp32 rows"); return GT_ERR_UNSUPPORTED; }
-      w.a2 = g_cat2.x2; w.a_split = g_cat2.split; w.lda2 = g_cat2.ld2;
-    }
-    if (rows__.rows) {
-      if (!w.w3) { gt_set_error("gt_linear_set_rows: needs a bound weight image"); return GT_ERR_UNSUPPORTED; }
-      w.out_rows = rows__.rows;
-      if (rows__.ln.out) {
-        if (w3_pick_nt(N) * 16 != N || act != 0 || a.thr || ldy != N) { gt_set_error("gt_linear_set_rows_layernorm: the row must fill one column block (ask gt_linear_rows_layernorm_ok)"); return GT_ERR_UNSUPPORTED; }
-        w.ln_w = rows__.ln.w; w.ln_b = rows__.ln.b; w.ln_out = rows__.ln.out; w.ln_mean = rows__.ln.mean; w.ln_rstd = rows__.ln.rstd;
-        w.ln_eps = rows__.ln.eps;
-      }
-    }
-    {
-      const bool on_rows_kernel = w.w3 && w3r_ok(x_dtype, y_dtype, w);
-      GtProfScope pk__(GT_PROF_GEMM_KERNEL, on_rows_kernel ? "k_lin3r[fwd]" : (w.w3 ? "k_lin3[fwd]" : "k_lin32[fwd]"), stream, {M, N, K, x_dtype, y_dtype, compute});
-      if (on_rows_kernel) w3r_launch(stream, w);   // rows straight into fragments (linear3r.h)
-      else if (w.w3) w3_launch<false>(x_dtype, y_dtype, stream, w);
-      else w32_launch<false>(x_dtype, y_dtype, stream, w);
-    }
-    GT_CHECK_LAUNCH();
-    return GT_OK;
-  }
-  // bf16 rows in and out with a bound fragment-order image of this weight (gt_w1_bind): the weight-stationary kernel (linear1.h)
-  if (x_dtype == GT_BF16 && y_dtype == GT_BF16 && compute == GT_BF16 && groups == 1 && act != 2 && M >= W1_MIN_M) {
-    if (const void* img = w1_lookup(weight, N, K, false)) {
-      L1Args l{};
-      l.a = (const gt_bf16*)x; l.img = (const unsigned char*)img; l.bias = bias; l.out = (gt_bf16*)y;
-      l.M = M; l.lda = ldx; l.ldo = ldy; l.N = (int)N; l.K = (int)K; l.act = act;
-      l.inv_keep = a.inv_keep; l.thr = a.thr; l.s0 = a.s0; l.s1 = a.s1;
-      // many rows, or a contraction the registers cannot hold: both operands through the LDS ring (linear2.h)
-      const bool ring = w2_take(l, w1_pick_ntw(N, K) != 0);
-      bool ok;
-      {
-        GtProfScope pk__(GT_PROF_GEMM_KERNEL, ring ? "k_lin2[fwd]" : "k_lin1[fwd]", stream, {M, N, K, x_dtype, y_dtype, compute});
-        ok = ring ? w2_launch(stream, l) : w1_launch(stream, l);
-      }
-      if (ok) { GT_CHECK_LAUNCH(); return GT_OK; }
-    }
-  }
-  const int bm = pick_bm(M, K, true);
-  a.ntiles = (int)gt_cdiv(N, BN);
-  dim3 grid((unsigned)(gt_cdiv(gt_cdiv(M, bm), 8) * 8 * a.ntiles), (unsigned)groups);
-  const int t0 = x_dtype, t1 = y_dtype;
-  {
-    GtProfScope pk__(GT_PROF_GEMM_KERNEL, "k_linear_fwd", stream, {M, N, K, x_dtype, y_dtype, compute});
-    if (bm == 64) GT_LIN_DISPATCH_BM(k_linear_fwd, 64, grid, a);
-    else GT_LIN_DISPATCH_BM(k_linear_fwd, 128, grid, a);
-  }
-  GT_CHECK_LAUNCH();
-  return GT_OK;
+// Y = dropout(gelu(X W^T + b)); gmul = gelu'(z) * dropout scale: what gt_linear_bwd_mul takes in place of the ReLU path's forward output
+extern "C" int gt_linear_fwd_gelu(int x_dtype, int y_dtype, int compute, const void* x, const float* weight, const float* bias, void* y, void* gmul,
+                                  int64_t M, int64_t N, int64_t K, int64_t ldx, int64_t ldy, float dropout_p, uint64_t seed, gt_stream_t stream_) {
+  LinFwd f{x_dtype, y_dtype, compute, x, weight, bias, y, M, N, K, ldx, ldy, 1, 0, 0, 2, dropout_p, seed, (hipStream_t)stream_};
+  f.gout = gmul;
+  f.map = take_map();
+  return lin_fwd(f);
 }
 
 extern "C" size_t gt_linear_bwd_workspace_bytes(int compute, int64_t M, int64_t N, int64_t K) {
@@ -1106,56 +1103,11 @@ extern "C" size_t gt_linear_bwd_workspace_bytes(int compute, int64_t M, int64_t 
   return (dw > dx ? dw : dx) + 256;  // the dx partials are consumed before dw reuses the space
 }
 
-extern "C" int gt_linear_bwd(int x_dtype, int y_dtype, int compute, const void* x, const float* weight, const void* dy,
-                             const void* y_for_mask, const void* dx_add1, const void* dx_add2, void* dx, float* dweight,
-                             float* dbias, int64_t M, int64_t N, int64_t K, float dropout_p, void* workspace,
-                             size_t workspace_bytes, gt_stream_t stream_) {
-  return gt_linear_bwd_ld(x_dtype, y_dtype, compute, x, weight, dy, y_for_mask, dx_add1, dx_add2, dx, dweight, dbias, M, N, K,
-                          N, dropout_p, workspace, workspace_bytes, stream_);
+extern "C" size_t gt_linear_bwd_grouped_workspace_bytes(int compute, int64_t M, int64_t N, int64_t K, int groups) {
+  return (size_t)(groups < 1 ? 1 : groups) * gt_linear_bwd_workspace_bytes(compute, M, N, K);
 }
 
-extern "C" int gt_linear_bwd_ld(int x_dtype, int y_dtype, int compute, const void* x, const float* weight, const void* dy,
-                                const void* y_for_mask, const void* dx_add1, const void* dx_add2, void* dx, float* dweight,
-                                float* dbias, int64_t M, int64_t N, int64_t K, int64_t ldy, float dropout_p,
-                                void* workspace, size_t workspace_bytes, gt_stream_t stream_) {
-  return gt_linear_bwd_ld2(x_dtype, y_dtype, compute, x, weight, dy, y_for_mask, dx_add1, dx_add2, dx, dweight, dbias, M, N, K,
-                           K, ldy, dropout_p, workspace, workspace_bytes, stream_);
-}
-
-// Options of ONE gt_linear_bwd* call that the plain entry points do not carry in their signatures: the variant entry points
-// below set them for the duration of their call to gt_linear_bwd_grouped (per host thread; cleared when that call returns).
-struct BnStatsReq {   // BatchNorm-backward statistics to accumulate in the dX epilogue (gt_linear_bwd_bnstats)
-  const float *x = nullptr, *mean = nullptr, *rstd = nullptr, *w = nullptr, *b = nullptr;
-  float* part = nullptr;
-  int64_t ldx = 0;
-  int relu = 0;
-};
-struct BwdCallOpts {
-  bool mul_mask = false;             // y_for_mask is a MULTIPLIER (gt_linear_bwd_mul), not a forward output
-  bool fork_dw_only = false;         // dW-only call that may still go to the overlap stream (gt_linear_bwd_dw_forked)
-  const float* weight_t = nullptr;   // W^T [K][N] prepared by the caller (gt_linear_bwd_wt): no transpose launch
-  BnStatsReq bns;                    // set by gt_linear_bwd_bnstats BEFORE the call it applies to
-  bool gate_out = false;             // y_for_mask [M][ldx] gates the dX OUTPUT (gt_linear_bwd_gate_out), dY is used as it is
-  const float* bcast = nullptr;      // dX += bcast[bcast_idx[row]] (gt_linear_bwd_bcast), set BEFORE the call it applies to
-  const int32_t* bcast_idx = nullptr;
-};
-thread_local BwdCallOpts g_opt;
-struct BwdOptScope {   // whatever was set is dropped when the call it was meant for returns
-  ~BwdOptScope() { g_opt = BwdCallOpts{}; }
-};
-
-extern "C" int gt_linear_bwd_ld2(int x_dtype, int y_dtype, int compute, const void* x, const float* weight, const void* dy,
-                                 const void* y_for_mask, const void* dx_add1, const void* dx_add2, void* dx, float* dweight,
-                                 float* dbias, int64_t M, int64_t N, int64_t K, int64_t ldx, int64_t ldy, float dropout_p,
-                                 void* workspace, size_t workspace_bytes, gt_stream_t stream_) {
-  return gt_linear_bwd_grouped(x_dtype, y_dtype, compute, x, weight, dy, y_for_mask, dx_add1, dx_add2, dx, dweight, dbias, M, N, K,
-                               ldx, ldy, 1, 0, 0, dropout_p, workspace, workspace_bytes, stream_);
-}
-
-// The dX of the NEXT gt_linear_bwd* call on this thread is the dy of a BatchNorm (input bn_x [M][ldx], saved mean / rstd, affine
-// w / b, ReLU behind it or not): its epilogue also writes the row-tile partial sums part[ceil(M/64)][2][K] of that BatchNorm's
-// backward (sum dy', sum dy' * xhat) -- what k_bn_bwd_partial would compute from a second pass over dy and bn_x.  Only the
-// exact-fp32 wide-tile path does this: ask gt_linear_bwd_bnstats_ok first; the request is dropped after the next call.
+// BatchNorm-backward statistics in the dX epilogue (include/graphtrans_hip.h): only the exact-fp32 wide-tile path does this
 extern "C" int gt_linear_bwd_bnstats_ok(int compute, int x_dtype, int y_dtype, int64_t M) {
   return (w32_eligible(compute, x_dtype, M, 1) && x_dtype == GT_F32 && y_dtype == GT_F32) ? 1 : 0;
 }
@@ -1173,25 +1125,19 @@ static bool bns_on_rows_kernel(int x_dtype, int y_dtype, const float* weight, in
   w.M = M; w.Nout = K; w.Kc = N; w.lda = ldy; w.ldo = ldx;
   return w3r_ok(GT_F32, GT_F32, w);
 }
-// Partial rows the dX call (weight [N][K], M rows) would write for a gt_linear_bwd_bnstats request under the CURRENT bindings of this
-// thread: ceil(M / 128) when the register-row bf16x6 kernel takes it (a bound image of W^T, M >= 12288), else gt_linear_bwd_bnstats_rows(M)
-// (the exact-fp32 kernel); 0 = no kernel does it for this call.
 extern "C" int64_t gt_linear_bwd_bnstats_rows_for(int compute, int x_dtype, int y_dtype, const float* weight, int64_t M, int64_t N, int64_t K) {
   if (!gt_linear_bwd_bnstats_ok(compute, x_dtype, y_dtype, M)) return 0;
   return bns_on_rows_kernel(x_dtype, y_dtype, weight, M, N, K, K, N) ? gt_cdiv(M, 128) : gt_cdiv(M, W32_BM);
 }
-extern "C" int gt_linear_bwd_bnstats(const float* bn_x, int64_t ldx, const float* mean, const float* rstd, const float* w,
-                                     const float* b, int relu, float* part) {
+extern "C" int gt_linear_bwd_bnstats(const float* bn_x, int64_t ldx, const float* mean, const float* rstd, const float* w, const float* b, int relu,
+                                     float* part) {
   GT_CHECK_ARG(bn_x && mean && rstd && w && b && part && ldx > 0, "null buffer");
-  BnStatsReq& q = g_opt.bns;
-  q.x = bn_x; q.ldx = ldx; q.mean = mean; q.rstd = rstd; q.w = w; q.b = b; q.relu = relu; q.part = part;
+  LinBwd& q = g_pending;
+  q.bn_x = bn_x; q.bn_ldx = ldx; q.bn_mean = mean; q.bn_rstd = rstd; q.bn_w = w; q.bn_b = b; q.bn_relu = relu; q.bn_part = part;
   return GT_OK;
 }
 
-// The dX of the NEXT gt_linear_bwd* call on this thread gets a broadcast addend: dx[m] += rows[idx[m]] (rows [.][K] fp32, pitch = the
-// dX pitch; idx int32 [M]) -- the gradient that reaches every node of a graph from the virtual-node update, d_t0[batch[m]]
-// (modules/gnn_module.py:219), added in the dX GEMM's epilogue instead of being written out per node first.  Only the kernel with
-// the rows in registers does this (csrc/linear3r.h): ask gt_linear_bwd_bcast_ok first; the request is dropped after the next call.
+// a broadcast addend in the dX epilogue, dx[m] += rows[idx[m]] (include/graphtrans_hip.h): only the kernel with the rows in registers (linear3r.h)
 extern "C" int gt_linear_bwd_bcast_ok(int compute, int x_dtype, int y_dtype, const float* weight, int64_t M, int64_t N, int64_t K) {
   if (!w32_eligible(compute, x_dtype, M, 1) || x_dtype != GT_F32 || y_dtype != GT_F32 || !w3_lookup(weight, N, K, true)) return 0;
   L32Args w{};
@@ -1201,22 +1147,11 @@ extern "C" int gt_linear_bwd_bcast_ok(int compute, int x_dtype, int y_dtype, con
 }
 extern "C" int gt_linear_bwd_bcast(const float* rows, const int32_t* idx) {
   GT_CHECK_ARG((rows == nullptr) == (idx == nullptr), "rows and idx go together");
-  g_opt.bcast = rows;
-  g_opt.bcast_idx = idx;
+  g_pending.bcast = rows;
+  g_pending.bcast_idx = idx;
   return GT_OK;
 }
 
-// gt_linear_bwd with the transposed weight W^T [K][N] supplied by the caller (weights do not change during a backward pass: one
-// gt_transpose per weight, off the critical path, replaces a transpose launch in front of every wide fp32 dX GEMM); NULL = as
-// gt_linear_bwd.  Paths that do not need W^T ignore it.
-extern "C" int gt_linear_bwd_wt(int x_dtype, int y_dtype, int compute, const void* x, const float* weight, const float* weight_t,
-                                const void* dy, const void* y_for_mask, const void* dx_add1, const void* dx_add2, void* dx,
-                                float* dweight, float* dbias, int64_t M, int64_t N, int64_t K, float dropout_p, void* workspace,
-                                size_t workspace_bytes, gt_stream_t stream_) {
-  g_opt.weight_t = weight_t;
-  return gt_linear_bwd_grouped(x_dtype, y_dtype, compute, x, weight, dy, y_for_mask, dx_add1, dx_add2, dx, dweight, dbias, M, N, K, K, N,
-                               1, 0, 0, dropout_p, workspace, workspace_bytes, stream_);
-}
 // out [K][N] = in [N][K]^T (fp32)
 extern "C" int gt_transpose(const float* in, float* out, int64_t N, int64_t K, gt_stream_t stream_) {
   GT_CHECK_ARG(in && out && N > 0 && K > 0, "bad arguments");
@@ -1225,427 +1160,475 @@ extern "C" int gt_transpose(const float* in, float* out, int64_t N, int64_t K, g
   return GT_OK;
 }
 
-// dW / db only (dx == NULL), and inside a gt_overlap_dw section still on the overlap stream, ordered behind everything queued on
-// `stream` so far: lets a caller start the weight gradient of a GEMM BEFORE its dX GEMM (the encoder layer's in_proj: a dW GEMM
-// that starts together with the next layer's first kernel is what the fused backward avoids)
-extern "C" int gt_linear_bwd_dw_forked(int x_dtype, int y_dtype, int compute, const void* x, const float* weight, const void* dy,
-                                       const void* y_for_mask, float* dweight, float* dbias, int64_t M, int64_t N, int64_t K,
-                                       int64_t ldx, int64_t ldy, float dropout_p, void* workspace, size_t workspace_bytes,
-                                       gt_stream_t stream_) {
-  g_opt.fork_dw_only = true;
-  return gt_linear_bwd_grouped(x_dtype, y_dtype, compute, x, weight, dy, y_for_mask, nullptr, nullptr, nullptr, dweight, dbias, M, N, K,
+namespace {
+// ---- backward: one function per kernel family, in order of preference -------------------------------------------------------------
+// What flows between them.  Each family either declines (it leaves the state as it is) or enqueues its launches and marks what it did.
+struct BwdState {
+  bool dx, dw;          // still to compute
+  const void* ymask;    // the gate the GEMMs still to run apply to dY (gt_linear_bwd_gate_out: gone once the gated dX is out)
+  int dx_splits;        // > 1: the tiled dX kernel left split-N partials in the workspace, a weight gradient must not fork behind it
+  float inv_keep;       // of the gate; 0 = multiplier mode (gt_gate)
+  size_t need;          // workspace bytes of the whole call
+  int64_t g_part;       // floats between the groups' partial buffers
+};
+
+// dW is off the critical path of the backward (only the optimizer reads it): inside a gt_overlap_dw_begin/_end section the weight gradient
+// of a call that also computes dX (or asks for it: gt_linear_bwd_dw_forked) runs on the side stream beside dX and whatever follows
+// (not while the launch profiler brackets this call: its events sit on the caller's stream only).  `site` = the calling family's own
+// condition.
+bool dw_will_fork(const LinBwd& c, bool site) {
+  return g_dw.active && c.stream == g_dw.main && (c.dx || c.fork_dw_only) && site && !(gt_prof_mask() & GT_PROF_LINEAR);
+}
+// -> the stream the weight gradient's launches go to, ordered behind everything queued on the caller's stream so far; when it is not
+// the caller's, dw_forked(workspace, bytes) books them afterwards
+hipStream_t dw_fork(const LinBwd& c, bool site) {
+  if (!dw_will_fork(c, site)) return c.stream;
+  (void)hipEventRecord(g_dw.ev_fork, g_dw.main);
+  (void)hipStreamWaitEvent(g_dw.side, g_dw.ev_fork, 0);
+  return g_dw.side;
+}
+void dw_book(const LinBwd& c, hipStream_t dw_stream) {
+  if (dw_stream != c.stream) dw_forked(c.workspace, c.workspace_bytes);
+}
+void small_dw(const LinBwd& c, const BwdState& s) {   // the one-wave-per-tile dW kernel (both short-M families)
+  // forked only with a workspace to book it under: the kernel itself needs none, but gt_overlap_dw_release(range) is how the
+  // caller learns when the dy / mask this GEMM reads (they live in the caller's workspace) may be overwritten
+  hipStream_t stream = dw_fork(c, s.dx_splits <= 1 && c.workspace && c.workspace_bytes);
+  SmallArgs sa{};
+  sa.x = (const float*)c.x; sa.w = c.weight; sa.dy = (const float*)c.dy; sa.ymask = (const float*)s.ymask;
+  sa.M = c.M; sa.N = c.N; sa.K = c.K; sa.ldx = c.ldx; sa.ldy = c.ldy; sa.inv_keep = s.inv_keep;
+  sa.out = c.dweight; sa.db = c.dbias;
+  {
+    GtProfScope pk__(GT_PROF_GEMM_KERNEL, "k_small_dw", stream, LIN_DIMS(c));
+    small_launch(SMALL_DW, c.compute, gt_cdiv(c.N, 32) * gt_cdiv(c.K, 16), c.M, stream, sa);
+  }
+  dw_book(c, stream);
+}
+int bwd_small(const LinBwd& c, BwdState& s) {   // short M (linear_small.h): no LDS, no partials
+  if (!small_eligible(c.x_dtype, c.y_dtype, c.M, c.N, c.K, c.ldx, c.ldy, c.groups)) return GT_OK;
+  if (s.dx) {
+    hipStream_t stream = c.stream;
+    SmallArgs sa{};
+    sa.w = c.weight; sa.dy = (const float*)c.dy; sa.ymask = (const float*)s.ymask; sa.add1 = (const float*)c.dx_add1; sa.add2 = (const float*)c.dx_add2;
+    sa.M = c.M; sa.N = c.N; sa.K = c.K; sa.ldx = c.ldx; sa.ldy = c.ldy; sa.inv_keep = s.inv_keep; sa.out = (float*)c.dx;
+    GtProfScope pk__(GT_PROF_GEMM_KERNEL, "k_small_dx", stream, LIN_DIMS(c));
+    small_launch(SMALL_DX, c.compute, gt_cdiv(c.M, 16) * gt_cdiv(c.K, 32), c.N, stream, sa);
+  }
+  if (s.dw) small_dw(c, s);
+  s.dx = s.dw = false;
+  return GT_OK;
+}
+// dX of a grouped big-M fp32 GEMM on the bound images of the groups' W^T (k_lin3, blockIdx.y = group)
+int bwd_grouped3_dx(const LinBwd& c, BwdState& s) {
+  if (!s.dx || c.groups <= 1 || !g3_eligible(c.compute, c.x_dtype, c.y_dtype, c.M, c.N, c.K, c.ldx, c.ldy) || c.bn_part || c.bcast || c.gate_out || c.dx2 ||
+      c.map.rows)
+    return GT_OK;
+  int64_t spacing = 0;
+  const void* img = w3_lookup_grouped(c.weight, c.N, c.K, c.groups, true, &spacing);
+  if (!img) return GT_OK;
+  hipStream_t stream = c.stream;
+  L32Args w{};
+  w.a = c.dy; w.amask = s.ymask; w.out = c.dx; w.add1 = c.dx_add1; w.add2 = c.dx_add2;
+  w.M = c.M; w.Nout = c.K; w.Kc = c.N; w.lda = c.ldy; w.ldw = c.N; w.ldo = c.ldx; w.inv_keep = s.inv_keep;
+  w.w3 = img; w.groups = c.groups; w.g_a = c.y_group_stride; w.g_o = c.x_group_stride; w.g_img = spacing;
+  GtProfScope pk__(GT_PROF_GEMM_KERNEL, "k_lin3[dx]", stream, LIN_DIMS(c));
+  w3_launch<true>(c.y_dtype, c.x_dtype, stream, w);
+  s.dx = false;
+  return GT_OK;
+}
+// the groups' weight gradients on the pipelined bf16x6 kernel (k_lin3r_dw, blockIdx.y = group) when their weights are bound
+int bwd_grouped3_dw(const LinBwd& c, BwdState& s) {
+  const int64_t M = c.M, N = c.N, K = c.K;
+  if (!s.dw || c.groups <= 1 || !g3_eligible(c.compute, c.x_dtype, c.y_dtype, M, N, K, c.ldx, c.ldy) || c.x2 || c.map.rows || !c.workspace ||
+      c.workspace_bytes < s.need)
+    return GT_OK;
+  int64_t spacing = 0;
+  L32DwArgs d{};
+  d.dy = c.dy; d.ymask = s.ymask; d.x = c.x; d.inv_keep = s.inv_keep;
+  d.M = M; d.N = N; d.K = K; d.ldy = c.ldy; d.ldx = c.ldx;
+  d.groups = c.groups; d.g_y = c.y_group_stride; d.g_x = c.x_group_stride;
+  if (!w3_lookup_grouped(c.weight, N, K, c.groups, false, &spacing) || !w3r_dw_ok(c.y_dtype, c.x_dtype, d)) return GT_OK;
+  // (the weight gradient alone goes to the overlap stream: a dX that the generic kernels below still owe stays on the caller's)
+  hipStream_t stream = dw_fork(c, true);
+  const int shape = w3r_dw_pick_shape(N, K);
+  const int nkb3 = (int)gt_cdiv(K, w3r_dw_xt(shape)), nnb3 = (int)gt_cdiv(N, w3r_dw_zt(shape));
+  int s3 = w3_dw_splits(M, nkb3 * nnb3 * c.groups);
+  const int cap = w32_dw_splits(M, (int)gt_cdiv(K, 64), (int)gt_cdiv(gt_cdiv(N, 16), w32_pick_nt(N)), false);   // a group's share of the workspace holds this many partial copies
+  if (s3 > cap) s3 = cap;
+  float* base = reinterpret_cast<float*>(c.workspace);
+  d.g_part = s.g_part;
+  d.part = base; d.dbpart = c.dbias ? base + (int64_t)s3 * N * K : nullptr;
+  d.splits = s3; d.nkb = nkb3; d.nnb = nnb3;
+  d.m_per_split = gt_cdiv(gt_cdiv(M, s3), 32) * 32;
+  dim3 grid3((unsigned)(gt_cdiv(s3, 8) * 8 * nkb3 * nnb3), (unsigned)c.groups);
+  {   // (the bracket holds the GEMM kernel alone: one rocprofv3 row; its fixed-order reduce is k_split_reduce's row)
+    GtProfScope pk__(GT_PROF_GEMM_KERNEL, "k_lin3r_dw", stream, LIN_DIMS(c));
+    w3r_launch_dw(grid3, stream, d, shape);
+  }
+  // (reduced right behind the GEMM, not deferred to the end of the backward: the PNA driver gathers the image gradients before that)
+  const int64_t len = N * K, len2 = c.dbias ? N : 0;
+  const int rg = (int)(gt_cdiv(len + len2, 256) < 2048 ? gt_cdiv(len + len2, 256) : 2048);
+  hipLaunchKernelGGL(k_split_reduce, dim3(rg, c.groups), dim3(256), 0, stream, (const float*)base, s3, len, c.dweight, (const float*)d.dbpart,
+                     len2, c.dbias, d.g_part);
+  dw_book(c, stream);
+  s.dw = false;
+  return GT_OK;
+}
+// dX = dZ (W^T)^T of the big-M exact-fp32 path: the forward-form kernel on the transposed weight; wt = where the workspace holds W^T
+int wide_dx(const LinBwd& c, const BwdState& s, float* wt) {
+  const int64_t M = c.M, N = c.N, K = c.K;
+  hipStream_t stream = c.stream;
+  const auto fail = [](const char* msg) { gt_set_error("%s", msg); return GT_ERR_UNSUPPORTED; };
+  const void* w3t = (c.y_dtype != GT_F32 && N % 8) ? nullptr : w3_lookup(c.weight, N, K, true);
+  if (w3t && c.bn_part && !bns_on_rows_kernel(c.x_dtype, c.y_dtype, c.weight, M, N, K, c.ldx, c.ldy)) w3t = nullptr;   // the exact kernel's epilogue then
+  if (w3t) {
+    wt = nullptr;   // the bound image of W^T: k_lin3, no transpose
+  } else if (c.weight_t) {
+    wt = const_cast<float*>(c.weight_t);   // read only
+  } else {
+    // W^T lives in the caller's workspace: a previous call's dW GEMM may still be running on the overlap stream with
+    // its partials in the same workspace (callers hand ONE workspace to consecutive GEMMs, e.g. the four of an encoder
+    // layer) -> wait for the forks that used this range (those on other workspaces keep running).
+    if (g_dw.active && stream == g_dw.main) dw_release(c.workspace, c.workspace_bytes);
+    hipLaunchKernelGGL(k_transpose32, dim3((unsigned)gt_cdiv(K, 32), (unsigned)gt_cdiv(N, 32)), dim3(256), 0, stream, c.weight, wt, N, K);
+  }
+  L32Args w{};
+  w.a = c.dy; w.amask = s.ymask; w.w = wt; w.out = c.dx; w.add1 = c.dx_add1; w.add2 = c.dx_add2;
+  w.M = M; w.Nout = K; w.Kc = N; w.lda = c.ldy; w.ldw = N; w.ldo = c.ldx; w.inv_keep = s.inv_keep;
+  if (c.bn_part && c.x_dtype == GT_F32 && c.y_dtype == GT_F32) {
+    w.bn_x = c.bn_x; w.bn_ldx = c.bn_ldx; w.bn_mean = c.bn_mean; w.bn_rstd = c.bn_rstd; w.bn_w = c.bn_w; w.bn_b = c.bn_b;
+    w.bn_relu = c.bn_relu; w.bn_part = c.bn_part;
+  }
+  w.w3 = w3t;
+  if (c.bcast) {
+    w.add_bc = c.bcast; w.add_bidx = c.bcast_idx;
+    if (!w3t || !w3r_ok(c.y_dtype, c.x_dtype, w)) return fail("gt_linear_bwd_bcast: this call does not run on the register-row kernel (ask gt_linear_bwd_bcast_ok)");
+  }
+  if (c.map.rows) {
+    if (!w3t) return fail("gt_linear_set_rows: needs the bound image of W^T");
+    w.a_rows = c.map.rows;
+  }
+  if (c.dx2) {
+    if (!w3t || c.dx_add1 || c.dx_add2) return fail("gt_linear_bwd_cat2: needs a bound weight image and no addends");
+    w.out2 = c.dx2; w.out_split = c.x_split; w.ldo2 = c.ldx2;
+  }
+  const bool on_rows_kernel = w3t && w3r_ok(c.y_dtype, c.x_dtype, w);
+  GtProfScope pk__(GT_PROF_GEMM_KERNEL, on_rows_kernel ? "k_lin3r[dx]" : (w3t ? "k_lin3[dx]" : "k_lin32[dx]"), stream, LIN_DIMS(c));
+  if (on_rows_kernel) w3r_launch(stream, w);
+  else if (w3t) w3_launch<true>(c.y_dtype, c.x_dtype, stream, w);
+  else w32_launch<true>(c.y_dtype, c.x_dtype, stream, w);
+  return GT_OK;
+}
+// dW of the big-M exact-fp32 path, split over M: the bf16x6 kernels on a bound weight (k_lin3r_dw / k_lin3_dw), else k_lin32_dw
+int wide_dw(const LinBwd& c, const BwdState& s, hipStream_t stream, float* part, int splits, int nt, int nkb, int nnb) {
+  const int64_t M = c.M, N = c.N, K = c.K;
+  L32DwArgs d{};
+  d.dy = c.dy; d.ymask = s.ymask; d.x = c.x; d.inv_keep = s.inv_keep;
+  d.M = M; d.N = N; d.K = K; d.ldy = c.ldy; d.ldx = c.ldx;
+  if (c.x2) { d.x2 = c.x2; d.x_split = c.x_split; d.ldx2 = c.ldx2; }
+  // weights with bound images run the bf16x6 dW kernel too (160 x 160 output tiles, split over M; linear3x.h)
+  const bool split3 = c.x_dtype == GT_F32 && w3_lookup(c.weight, N, K, false) != nullptr && (c.y_dtype == GT_F32 || N % 8 == 0);
+  if (c.map.rows && !split3) { gt_set_error("gt_linear_set_rows: needs the bound weight image"); return GT_ERR_UNSUPPORTED; }
+  d.dy_rows = c.map.rows;
+  if (split3) {
+    d.nkb = (int)gt_cdiv(K, W3D_T); d.nnb = (int)gt_cdiv(N, W3D_T);
+    splits = w3_dw_splits(M, d.nkb * d.nnb);
+    const int cap = w32_dw_splits(M, nkb, nnb, false);   // the workspace is sized for this many partial copies
+    if (splits > cap) splits = cap;
+    d.m_per_split = gt_cdiv(gt_cdiv(M, splits), 32) * 32;
+  } else {
+    d.nkb = nkb; d.nnb = nnb;
+    d.m_per_split = gt_cdiv(gt_cdiv(M, splits), 16) * 16;
+  }
+  bool deferred;
+  d.part = dw_part(part, splits, N, K, &deferred);
+  d.dbpart = c.dbias ? d.part + (size_t)splits * N * K : nullptr;
+  d.splits = splits;
+  dim3 grid((unsigned)(gt_cdiv(splits, 8) * 8 * d.nkb * d.nnb));
+  const bool pipelined = split3 && w3r_dw_ok(c.y_dtype, c.x_dtype, d);
+  {
+    GtProfScope pk__(GT_PROF_GEMM_KERNEL, pipelined ? "k_lin3r_dw" : (split3 ? "k_lin3_dw" : "k_lin32_dw"), stream, LIN_DIMS(c));
+    if (pipelined) w3r_launch_dw(grid, stream, d);   // stages pipelined (linear3r.h)
+    else if (split3 && c.y_dtype == GT_F32) w3_launch_dw<float, float>(grid, stream, d);
+    else if (split3) w3_launch_dw<gt_bf16, float>(grid, stream, d);
+    else if (c.y_dtype == GT_F32) w32_launch_dw_nt<float, float>(nt, grid, stream, d);
+    else w32_launch_dw_nt<gt_bf16, float>(nt, grid, stream, d);
+  }
+  dw_reduce(stream, deferred, d.part, splits, N * K, c.dweight, d.dbpart, c.dbias ? N : 0, c.dbias);
+  return GT_OK;
+}
+int bwd_wide(const LinBwd& c, BwdState& s) {   // big-M exact-fp32 compute (linear32.h, linear3x.h, linear3r.h): dX and dW
+  if (!w32_eligible(c.compute, c.x_dtype, c.M, c.groups)) return GT_OK;
+  const int64_t M = c.M, N = c.N, K = c.K;
+  if (!c.workspace || c.workspace_bytes < s.need) {
+    gt_set_error("gt_linear_bwd: workspace too small (%zu < %zu)", c.workspace_bytes, s.need);
+    return GT_ERR_WORKSPACE;
+  }
+  const int nt = w32_pick_nt(N);
+  const int nkb = (int)gt_cdiv(K, 64), nnb = (int)gt_cdiv(gt_cdiv(N, 16), nt);
+  // (a weight gradient that will share the chip with the critical path runs fewer splits, unless the optimizer waits for it: w32_dw_splits)
+  const int splits = w32_dw_splits(M, nkb, nnb, dw_will_fork(c, s.dw) && !g_dw.urgent);
+  float* part = reinterpret_cast<float*>(c.workspace);
+  float* wt = part + (size_t)w32_dw_splits(M, nkb, nnb, false) * (size_t)(N * K + N) + 64;   // behind the larger partial area
+  wt = reinterpret_cast<float*>(((uintptr_t)wt + 255) & ~(uintptr_t)255);
+  if (s.dx)
+    if (const int rc = wide_dx(c, s, wt)) return rc;
+  if (s.dw) {
+    hipStream_t stream = dw_fork(c, true);
+    if (const int rc = wide_dw(c, s, stream, part, splits, nt, nkb, nnb)) return rc;
+    dw_book(c, stream);
+  }
+  s.dx = s.dw = false;
+  return GT_OK;
+}
+// dX = dY W on the bound image of W^T (linear1.h / linear2.h); a gate here applies to the OUTPUT columns (gt_linear_bwd_gate_out)
+int bwd_bf16_image_dx(const LinBwd& c, BwdState& s) {
+  if (!s.dx || c.x_dtype != GT_BF16 || c.y_dtype != GT_BF16 || c.compute != GT_BF16 || c.groups != 1 || c.M < W1_MIN_M || (c.y_for_mask && !c.gate_out))
+    return GT_OK;
+  const void* img = w1_lookup(c.weight, c.N, c.K, true);
+  if (!img) return GT_OK;
+  hipStream_t stream = c.stream;
+  L1Args l{};
+  l.a = (const gt_bf16*)c.dy; l.img = (const unsigned char*)img; l.out = (gt_bf16*)c.dx;
+  l.gate = c.gate_out ? (const gt_bf16*)c.y_for_mask : nullptr; l.gate_inv_keep = s.inv_keep;
+  l.add1 = (const gt_bf16*)c.dx_add1; l.add2 = (const gt_bf16*)c.dx_add2;
+  l.M = c.M; l.lda = c.ldy; l.ldo = c.ldx; l.N = (int)c.K; l.K = (int)c.N;
+  const bool ring = w2_take(l, w1_pick_ntw(c.K, c.N) != 0);
+  GtProfScope pk__(GT_PROF_GEMM_KERNEL, ring ? "k_lin2[dx]" : "k_lin1[dx]", stream, LIN_DIMS(c));
+  s.dx = !(ring ? w2_launch(stream, l) : w1_launch(stream, l));
+  return GT_OK;
+}
+// gt_linear_bwd_gate_out: only the family above gates the dX output; behind it the gate is spent
+int bwd_gate_out_spent(const LinBwd& c, BwdState& s) {
+  if (!c.gate_out) return GT_OK;
+  if (s.dx) { gt_set_error("gt_linear_bwd_gate_out: not covered (ask gt_linear_bwd_gate_out_ok)"); return GT_ERR_UNSUPPORTED; }
+  s.ymask = nullptr;   // the gate belongs to the dX output, not to dY: the weight gradient below reads dY as it is
+  return GT_OK;
+}
+// the prediction heads: the contraction is their 25 010 columns (linear_heads.h)
+// (shape matching alone must not route a general GEMM with per-call options here: k_heads_dx knows none of them)
+int bwd_heads_dx(const LinBwd& c, BwdState& s) {
+  if (!s.dx || s.ymask || c.mul_mask || c.bn_part || c.gate_out || c.dropout_p != 0.f ||
+      !heads_shape_ok(c.x_dtype, c.y_dtype, c.M, c.N, c.K, c.ldx, c.ldy, c.groups) || !c.workspace ||
+      c.workspace_bytes < heads_dx_workspace_bytes(c.M, c.N))
+    return GT_OK;
+  hipStream_t stream = c.stream;
+  HeadsArgs h{};
+  h.w = c.weight; h.dy = (const float*)c.dy; h.M = c.M; h.N = c.N; h.ldx = c.ldx; h.ldy = c.ldy;
+  GtProfScope pk__(GT_PROF_GEMM_KERNEL, "k_heads_dx+reduce", stream, LIN_DIMS(c));
+  heads_launch_dx(c.compute, stream, h, c.workspace, (float*)c.dx, (const float*)c.dx_add1, (const float*)c.dx_add2);
+  s.dx = false;
+  return GT_OK;
+}
+LinArgs tiled_args(const LinBwd& c, const BwdState& s) {
+  LinArgs a{};
+  a.w = c.weight; a.a = c.dy; a.ymask = s.ymask; a.x = c.x; a.M = c.M; a.N = c.N; a.K = c.K; a.ldy = c.ldy; a.ldx = c.ldx;
+  a.add1 = c.dx_add1; a.add2 = c.dx_add2; a.inv_keep = s.inv_keep;
+  a.g_x = c.x_group_stride; a.g_y = c.y_group_stride; a.g_w = c.N * c.K; a.g_b = c.N; a.g_part = s.g_part;
+  return a;
+}
+int bwd_tiled_dx(const LinBwd& c, BwdState& s) {
+  if (!s.dx) return GT_OK;
+  const int64_t M = c.M, N = c.N, K = c.K;
+  hipStream_t stream = c.stream;
+  const int compute = c.compute, bm = pick_bm(M);
+  // split-N partials are plain fp32 sums: only for fp32 dX without fused addends (and not for grouped launches)
+  int splits = (c.x_dtype == GT_F32 && !c.dx_add1 && !c.dx_add2 && c.ldx == K && c.groups == 1) ? dx_splits(M, N, K, bm) : 1;
+  if (splits > 1 && (!c.workspace || c.workspace_bytes < s.need)) splits = 1;
+  LinArgs a = tiled_args(c, s);
+  a.splits = splits;
+  a.n_per_split = gt_cdiv(gt_cdiv(N, splits), 64) * 64;
+  a.out = splits > 1 ? c.workspace : c.dx;
+  a.ntiles = (int)gt_cdiv(K, BN);
+  dim3 grid((unsigned)(gt_cdiv(gt_cdiv(M, bm), 8) * 8 * a.ntiles), (unsigned)c.groups, (unsigned)splits);
+  const int t0 = c.y_dtype, t1 = c.x_dtype;
+  GtProfScope pk__(GT_PROF_GEMM_KERNEL, "k_linear_dx", stream, LIN_DIMS(c));
+  if (bm == 64) GT_LIN_DISPATCH_BM(k_linear_dx, 64, grid, a);
+  else GT_LIN_DISPATCH_BM(k_linear_dx, 128, grid, a);
+  if (splits > 1) {
+    const int64_t len = M * K;
+    const int rg = (int)(gt_cdiv(len, 256) < 2048 ? gt_cdiv(len, 256) : 2048);
+    hipLaunchKernelGGL(k_split_reduce, dim3(rg), dim3(256), 0, stream, (const float*)c.workspace, splits, len,
+                       reinterpret_cast<float*>(c.dx), (const float*)nullptr, (int64_t)0, (float*)nullptr, (int64_t)0);
+  }
+  s.dx = false;
+  s.dx_splits = splits;
+  return GT_OK;
+}
+int bwd_small_wide_dw(const LinBwd& c, BwdState& s) {   // wide short-M GEMM: dW on the one-wave-per-tile kernel
+  if (!s.dw || !small_wide_ok(c.x_dtype, c.y_dtype, c.M, c.K, c.ldx, c.ldy, c.groups)) return GT_OK;
+  small_dw(c, s);
+  s.dw = false;
+  return GT_OK;
+}
+// dW split over M with a fixed-order reduce: bf16 token rows on the LDS-DMA ring kernel (linear_dw16.h), everything else on the tiled one
+int bwd_split_dw(const LinBwd& c, BwdState& s) {
+  if (!s.dw) return GT_OK;
+  const int64_t M = c.M, N = c.N, K = c.K;
+  const int compute = c.compute, splits = dw_splits(M, N, K, compute);
+  if (!c.workspace || c.workspace_bytes < s.need) {
+    gt_set_error("gt_linear_bwd: workspace too small (%zu < %zu)", c.workspace_bytes, s.need);
+    return GT_ERR_WORKSPACE;
+  }
+  hipStream_t stream = dw_fork(c, s.dx_splits <= 1);
+  if (dw16_ok(c.x_dtype, c.y_dtype, compute, c.x, c.dy, s.ymask, M, N, K, c.ldx, c.ldy, c.groups)) {
+    Dw16Args d{};
+    d.dy = (const gt_bf16*)c.dy; d.x = (const gt_bf16*)c.x; d.M = M; d.N = N; d.K = K; d.ldy = c.ldy; d.ldx = c.ldx;
+    d.splits = dw16_splits(M, N, K, splits);
+    d.m_per_split = gt_cdiv(gt_cdiv(M, d.splits), D16_ROWS) * D16_ROWS;
+    bool deferred;
+    d.part = dw_part(reinterpret_cast<float*>(c.workspace), d.splits, N, K, &deferred);
+    d.dbpart = c.dbias ? d.part + (size_t)d.splits * N * K : nullptr;
+    d.ntx = (int)(N / D16_T);
+    d.ntiles = d.ntx * (int)(K / D16_T);
+    {
+      GtProfScope pk__(GT_PROF_GEMM_KERNEL, "k_dw16", stream, LIN_DIMS(c));
+      hipLaunchKernelGGL(k_dw16, dim3((unsigned)(gt_cdiv(d.splits, 8) * 8 * d.ntiles)), dim3(256), 0, stream, d);
+    }
+    dw_reduce(stream, deferred, d.part, d.splits, N * K, c.dweight, d.dbpart, c.dbias ? N : 0, c.dbias);
+  } else {
+    const int64_t bmc = compute == GT_BF16 ? 64 : 32;
+    LinArgs a = tiled_args(c, s);
+    a.splits = splits;
+    a.m_per_split = gt_cdiv(gt_cdiv(M, splits), bmc) * bmc;
+    a.out = c.workspace;
+    a.dbpart = c.dbias ? reinterpret_cast<float*>(c.workspace) + (size_t)splits * N * K : nullptr;
+    a.ntx = (int)gt_cdiv(N, BN);
+    a.ntiles = a.ntx * (int)gt_cdiv(K, BN);
+    dim3 grid((unsigned)(gt_cdiv(splits, 8) * 8 * a.ntiles), (unsigned)c.groups);
+    const int t0 = c.y_dtype, t1 = c.x_dtype;
+    {
+      GtProfScope pk__(GT_PROF_GEMM_KERNEL, "k_linear_dw", stream, LIN_DIMS(c));
+      GT_LIN_DISPATCH(k_linear_dw, grid, a);
+    }
+    const int64_t len = N * K, len2 = c.dbias ? N : 0;
+    const int rg = (int)(gt_cdiv(len + len2, 256) < 2048 ? gt_cdiv(len + len2, 256) : 2048);
+    hipLaunchKernelGGL(k_split_reduce, dim3(rg, c.groups), dim3(256), 0, stream, (const float*)c.workspace, splits, len, c.dweight,
+                       (const float*)a.dbpart, len2, c.dbias, a.g_part);
+  }
+  dw_book(c, stream);
+  s.dw = false;
+  return GT_OK;
+}
+}  // namespace
+
+int lin_bwd(const LinBwd& c) {
+  const char* fn = "gt_linear_bwd_grouped";
+  if (c.bcast && c.dx && !gt_linear_bwd_bcast_ok(c.compute, c.x_dtype, c.y_dtype, c.weight, c.M, c.N, c.K)) {
+    gt_set_error("gt_linear_bwd_bcast: this call does not run on the register-row kernel (ask gt_linear_bwd_bcast_ok)");
+    return GT_ERR_UNSUPPORTED;
+  }
+  LIN_CHECK_ARG(fn, !c.map.rows || (c.groups == 1 && !c.y_for_mask && !c.bn_part && !c.map.ln_out &&
+                                    rows_eligible(c.compute, c.x_dtype, c.y_dtype, c.weight, c.M, c.N, c.K)),
+                "gt_linear_set_rows: this GEMM does not take a row map (ask gt_linear_rows_ok)");
+  int rc = check_call(fn, "gt_linear_bwd", c.x_dtype, c.y_dtype, c.compute, c.M, c.N, c.K, c.ldx, c.ldy, c.x2 ? c.x_split : c.K, c.groups,
+                      c.x_group_stride, c.y_group_stride);
+  if (rc) return rc;
+  LIN_CHECK_ARG(fn, c.weight && c.dy, "null buffer");
+  LIN_CHECK_ARG(fn, c.dx || c.dweight, "nothing to compute");
+  LIN_CHECK_ARG(fn, !c.dweight || c.x, "dweight needs x");
+  LIN_CHECK_ARG(fn, c.dropout_p >= 0.f && c.dropout_p < 1.f, "dropout_p must be in [0,1)");
+  GtProfScope prof__(GT_PROF_LINEAR, c.dx ? (c.dweight ? "gt_linear_bwd" : "gt_linear_bwd_dx") : "gt_linear_bwd_dw", c.stream, LIN_DIMS(c));
+  if (c.M == 0) {
+    if (c.dweight) (void)hipMemsetAsync(c.dweight, 0, (size_t)c.groups * c.N * c.K * sizeof(float), c.stream);
+    if (c.dbias) (void)hipMemsetAsync(c.dbias, 0, (size_t)c.groups * c.N * sizeof(float), c.stream);
+    return GT_OK;
+  }
+  const size_t need1 = gt_linear_bwd_workspace_bytes(c.compute, c.M, c.N, c.K);   // per group
+  BwdState s{};
+  s.dx = c.dx != nullptr; s.dw = c.dweight != nullptr; s.ymask = c.y_for_mask;
+  s.inv_keep = c.mul_mask ? 0.f : 1.0f / (1.0f - c.dropout_p);
+  s.need = (size_t)c.groups * need1;
+  s.g_part = (int64_t)(need1 / sizeof(float));
+  static int (*const families[])(const LinBwd&, BwdState&) = {
+      bwd_small, bwd_grouped3_dx, bwd_grouped3_dw, bwd_wide, bwd_bf16_image_dx, bwd_gate_out_spent, bwd_heads_dx, bwd_tiled_dx, bwd_small_wide_dw,
+      bwd_split_dw};
+  for (auto family : families) {
+    if ((rc = family(c, s)) != GT_OK) return rc;
+    if (!s.dx && !s.dw) break;
+  }
+  hipError_t e = hipGetLastError();
+  if (e != hipSuccess) { gt_set_error("%s: launch failed: %s", fn, hipGetErrorString(e)); return GT_ERR_LAUNCH; }
+  return GT_OK;
+}
+
+extern "C" int gt_linear_bwd(int x_dtype, int y_dtype, int compute, const void* x, const float* weight, const void* dy, const void* y_for_mask,
+                             const void* dx_add1, const void* dx_add2, void* dx, float* dweight, float* dbias, int64_t M, int64_t N, int64_t K,
+                             float dropout_p, void* workspace, size_t workspace_bytes, gt_stream_t stream_) {
+  return gt_linear_bwd_grouped(x_dtype, y_dtype, compute, x, weight, dy, y_for_mask, dx_add1, dx_add2, dx, dweight, dbias, M, N, K, K, N, 1, 0, 0,
+                               dropout_p, workspace, workspace_bytes, stream_);
+}
+
+extern "C" int gt_linear_bwd_ld(int x_dtype, int y_dtype, int compute, const void* x, const float* weight, const void* dy, const void* y_for_mask,
+                                const void* dx_add1, const void* dx_add2, void* dx, float* dweight, float* dbias, int64_t M, int64_t N, int64_t K,
+                                int64_t ldy, float dropout_p, void* workspace, size_t workspace_bytes, gt_stream_t stream_) {
+  return gt_linear_bwd_grouped(x_dtype, y_dtype, compute, x, weight, dy, y_for_mask, dx_add1, dx_add2, dx, dweight, dbias, M, N, K, K, ldy, 1, 0, 0,
+                               dropout_p, workspace, workspace_bytes, stream_);
+}
+
+extern "C" int gt_linear_bwd_ld2(int x_dtype, int y_dtype, int compute, const void* x, const float* weight, const void* dy, const void* y_for_mask,
+                                 const void* dx_add1, const void* dx_add2, void* dx, float* dweight, float* dbias, int64_t M, int64_t N, int64_t K,
+                                 int64_t ldx, int64_t ldy, float dropout_p, void* workspace, size_t workspace_bytes, gt_stream_t stream_) {
+  return gt_linear_bwd_grouped(x_dtype, y_dtype, compute, x, weight, dy, y_for_mask, dx_add1, dx_add2, dx, dweight, dbias, M, N, K,
                                ldx, ldy, 1, 0, 0, dropout_p, workspace, workspace_bytes, stream_);
+}
+
+extern "C" int gt_linear_bwd_grouped(int x_dtype, int y_dtype, int compute, const void* x, const float* weight, const void* dy,
+                                     const void* y_for_mask, const void* dx_add1, const void* dx_add2, void* dx, float* dweight, float* dbias,
+                                     int64_t M, int64_t N, int64_t K, int64_t ldx, int64_t ldy, int groups, int64_t x_group_stride,
+                                     int64_t y_group_stride, float dropout_p, void* workspace, size_t workspace_bytes, gt_stream_t stream_) {
+  LinBwd c{x_dtype, y_dtype, compute, x, weight, dy, y_for_mask, dx_add1, dx_add2, dx, dweight, dbias, M, N, K, ldx, ldy, groups,
+               x_group_stride, y_group_stride, dropout_p, workspace, workspace_bytes, (hipStream_t)stream_};
+  take_bwd(c);
+  return lin_bwd(c);
+}
+
+// W^T [K][N] supplied by the caller (one gt_transpose per weight and backward pass instead of one in front of every wide fp32 dX GEMM)
+extern "C" int gt_linear_bwd_wt(int x_dtype, int y_dtype, int compute, const void* x, const float* weight, const float* weight_t, const void* dy,
+                                const void* y_for_mask, const void* dx_add1, const void* dx_add2, void* dx, float* dweight, float* dbias, int64_t M,
+                                int64_t N, int64_t K, float dropout_p, void* workspace, size_t workspace_bytes, gt_stream_t stream_) {
+  LinBwd c{x_dtype, y_dtype, compute, x, weight, dy, y_for_mask, dx_add1, dx_add2, dx, dweight, dbias, M, N, K, K, N, 1, 0, 0, dropout_p,
+               workspace, workspace_bytes, (hipStream_t)stream_};
+  take_bwd(c);
+  c.weight_t = weight_t;
+  return lin_bwd(c);
+}
+
+// dW / db only, inside a gt_overlap_dw section still on the overlap stream: a caller can start a GEMM's weight gradient BEFORE its dX GEMM
+// (the encoder layer's in_proj: a dW GEMM that starts together with the next layer's first kernel is what the fused backward avoids)
+extern "C" int gt_linear_bwd_dw_forked(int x_dtype, int y_dtype, int compute, const void* x, const float* weight, const void* dy,
+                                       const void* y_for_mask, float* dweight, float* dbias, int64_t M, int64_t N, int64_t K, int64_t ldx,
+                                       int64_t ldy, float dropout_p, void* workspace, size_t workspace_bytes, gt_stream_t stream_) {
+  LinBwd c{x_dtype, y_dtype, compute, x, weight, dy, y_for_mask, nullptr, nullptr, nullptr, dweight, dbias, M, N, K, ldx, ldy, 1, 0, 0,
+               dropout_p, workspace, workspace_bytes, (hipStream_t)stream_};
+  take_bwd(c);
+  c.fork_dw_only = true;
+  return lin_bwd(c);
 }
 
 // gt_linear_bwd_dw_forked for a layer whose forward saved a multiplier (gt_linear_fwd_gelu): dZ = dY * gmul
 extern "C" int gt_linear_bwd_mul_dw_forked(int x_dtype, int y_dtype, int compute, const void* x, const float* weight, const void* dy,
-                                           const void* gmul, float* dweight, float* dbias, int64_t M, int64_t N, int64_t K,
-                                           int64_t ldx, int64_t ldy, void* workspace, size_t workspace_bytes, gt_stream_t stream_) {
+                                           const void* gmul, float* dweight, float* dbias, int64_t M, int64_t N, int64_t K, int64_t ldx, int64_t ldy,
+                                           void* workspace, size_t workspace_bytes, gt_stream_t stream_) {
   GT_CHECK_ARG(gmul, "gt_linear_bwd_mul_dw_forked needs the multiplier");
-  g_opt.fork_dw_only = true;
-  g_opt.mul_mask = true;
-  return gt_linear_bwd_grouped(x_dtype, y_dtype, compute, x, weight, dy, gmul, nullptr, nullptr, nullptr, dweight, dbias, M, N, K, ldx,
-                               ldy, 1, 0, 0, 0.f, workspace, workspace_bytes, stream_);
+  LinBwd c{x_dtype, y_dtype, compute, x, weight, dy, gmul, nullptr, nullptr, nullptr, dweight, dbias, M, N, K, ldx, ldy, 1, 0, 0, 0.f,
+               workspace, workspace_bytes, (hipStream_t)stream_};
+  take_bwd(c);
+  c.fork_dw_only = true;
+  c.mul_mask = true;
+  return lin_bwd(c);
 }
 
 // backward of gt_linear_fwd_gelu: `gmul` is the multiplier that forward saved (dZ = dY * gmul); everything else as gt_linear_bwd_ld2
-extern "C" int gt_linear_bwd_mul(int x_dtype, int y_dtype, int compute, const void* x, const float* weight, const void* dy,
-                                 const void* gmul, const void* dx_add1, const void* dx_add2, void* dx, float* dweight,
-                                 float* dbias, int64_t M, int64_t N, int64_t K, int64_t ldx, int64_t ldy, void* workspace,
-                                 size_t workspace_bytes, gt_stream_t stream_) {
+extern "C" int gt_linear_bwd_mul(int x_dtype, int y_dtype, int compute, const void* x, const float* weight, const void* dy, const void* gmul,
+                                 const void* dx_add1, const void* dx_add2, void* dx, float* dweight, float* dbias, int64_t M, int64_t N, int64_t K,
+                                 int64_t ldx, int64_t ldy, void* workspace, size_t workspace_bytes, gt_stream_t stream_) {
   GT_CHECK_ARG(gmul, "gt_linear_bwd_mul needs the multiplier");
-  g_opt.mul_mask = true;
-  return gt_linear_bwd_grouped(x_dtype, y_dtype, compute, x, weight, dy, gmul, dx_add1, dx_add2, dx, dweight, dbias, M, N, K, ldx, ldy,
-                               1, 0, 0, 0.f, workspace, workspace_bytes, stream_);
-}
-
-extern "C" size_t gt_linear_bwd_grouped_workspace_bytes(int compute, int64_t M, int64_t N, int64_t K, int groups) {
-  return (size_t)(groups < 1 ? 1 : groups) * gt_linear_bwd_workspace_bytes(compute, M, N, K);
-}
-
-extern "C" int gt_linear_bwd_grouped(int x_dtype, int y_dtype, int compute, const void* x, const float* weight, const void* dy,
-                                     const void* y_for_mask, const void* dx_add1, const void* dx_add2, void* dx, float* dweight,
-                                     float* dbias, int64_t M, int64_t N, int64_t K, int64_t ldx, int64_t ldy, int groups,
-                                     int64_t x_group_stride, int64_t y_group_stride, float dropout_p, void* workspace,
-                                     size_t workspace_bytes, gt_stream_t stream_) {
-  BwdOptScope opt_scope__;   // the per-call options live for exactly this call
-  if (g_opt.bcast && dx && !gt_linear_bwd_bcast_ok(compute, x_dtype, y_dtype, weight, M, N, K)) {
-    gt_set_error("gt_linear_bwd_bcast: this call does not run on the register-row kernel (ask gt_linear_bwd_bcast_ok)");
-    return GT_ERR_UNSUPPORTED;
-  }
-  const RowsTake rows__;
-  GT_CHECK_ARG(!rows__.rows || (groups == 1 && !y_for_mask && !g_opt.bns.part && !rows__.ln.out && rows_eligible(compute, x_dtype, y_dtype, weight, M, N, K)),
-               "gt_linear_set_rows: this GEMM does not take a row map (ask gt_linear_rows_ok)");
-  GT_CHECK_ARG(groups >= 1 && groups <= 65535, "1..65535 groups");
-  GT_CHECK_ARG(groups == 1 || (x_group_stride % (x_dtype == GT_BF16 ? 8 : 4) == 0 && y_group_stride % (y_dtype == GT_BF16 ? 8 : 4) == 0 &&
-                               (N * K) % 4 == 0),
-               "group strides must keep 16-byte alignment");
-  int rc = check_lin("gt_linear_bwd", x_dtype, y_dtype, compute, M, N, K, ldy);
-  if (rc == GT_OK && (ldx < (g_cat2.x2 ? g_cat2.split : K) || ldx % (x_dtype == GT_BF16 ? 8 : 4))) {   // (cat2: the first matrix holds columns [0, split))
-    gt_set_error("gt_linear_bwd: ldx (%lld) must be >= K and a multiple of 16 bytes", (long long)ldx);
-    rc = GT_ERR_UNSUPPORTED;
-  }
-  if (rc) return rc;
-  GT_CHECK_ARG(weight && dy, "null buffer");
-  GT_CHECK_ARG(dx || dweight, "nothing to compute");
-  GT_CHECK_ARG(!dweight || x, "dweight needs x");
-  GT_CHECK_ARG(dropout_p >= 0.f && dropout_p < 1.f, "dropout_p must be in [0,1)");
-  hipStream_t stream = (hipStream_t)stream_;
-  GtProfScope prof__(GT_PROF_LINEAR, dx ? (dweight ? "gt_linear_bwd" : "gt_linear_bwd_dx") : "gt_linear_bwd_dw", stream_,
-                     {M, N, K, x_dtype, y_dtype, compute});
-  LinArgs a{};
-  a.w = weight; a.a = dy; a.ymask = y_for_mask; a.x = x; a.M = M; a.N = N; a.K = K; a.ldy = ldy; a.ldx = ldx;
-  a.add1 = dx_add1; a.add2 = dx_add2;
-  a.inv_keep = g_opt.mul_mask ? 0.f : 1.0f / (1.0f - dropout_p);   // 0 = multiplier mode (gt_gate)
-  a.g_x = x_group_stride; a.g_y = y_group_stride; a.g_w = N * K; a.g_b = N;
-  if (M == 0) {
-    if (dweight) (void)hipMemsetAsync(dweight, 0, (size_t)groups * N * K * sizeof(float), stream);
-    if (dbias) (void)hipMemsetAsync(dbias, 0, (size_t)groups * N * sizeof(float), stream);
-    return GT_OK;
-  }
-  const size_t need1 = gt_linear_bwd_workspace_bytes(compute, M, N, K);   // per group
-  const size_t need = (size_t)groups * need1;
-  a.g_part = (int64_t)(need1 / sizeof(float));
-  if (small_eligible(x_dtype, y_dtype, M, N, K, ldx, ldy, groups)) {
-    SmallArgs sa{};
-    sa.x = (const float*)x; sa.w = weight; sa.dy = (const float*)dy; sa.ymask = (const float*)y_for_mask;
-    sa.add1 = (const float*)dx_add1; sa.add2 = (const float*)dx_add2; sa.M = M; sa.N = N; sa.K = K; sa.ldx = ldx; sa.ldy = ldy;
-    sa.inv_keep = a.inv_keep;
-    if (dx) {
-      sa.out = (float*)dx;
-      GtProfScope pk__(GT_PROF_GEMM_KERNEL, "k_small_dx", stream, {M, N, K, x_dtype, y_dtype, compute});
-      small_launch(SMALL_DX, compute, gt_cdiv(M, 16) * gt_cdiv(K, 32), N, stream, sa);
-    }
-    if (dweight) {
-      // forked only with a workspace to book it under: the kernel itself needs none, but gt_overlap_dw_release(range) is how the
-      // caller learns when the dy / mask this GEMM reads (they live in the caller's workspace) may be overwritten
-      const bool forked = g_dw.active && stream == g_dw.main && (dx || g_opt.fork_dw_only) && workspace && workspace_bytes &&
-                          !(gt_prof_mask() & GT_PROF_LINEAR);
-      if (forked) {
-        (void)hipEventRecord(g_dw.ev_fork, stream);
-        (void)hipStreamWaitEvent(g_dw.side, g_dw.ev_fork, 0);
-        stream = g_dw.side;
-      }
-      sa.out = dweight; sa.db = dbias;
-      {
-        GtProfScope pk__(GT_PROF_GEMM_KERNEL, "k_small_dw", stream, {M, N, K, x_dtype, y_dtype, compute});
-        small_launch(SMALL_DW, compute, gt_cdiv(N, 32) * gt_cdiv(K, 16), M, stream, sa);
-      }
-      if (forked) dw_forked(workspace, workspace_bytes);
-    }
-    GT_CHECK_LAUNCH();
-    return GT_OK;
-  }
-  bool dx_done = false;
-  if (dx && groups > 1 && g3_eligible(compute, x_dtype, y_dtype, M, N, K, ldx, ldy) && !g_opt.bns.part && !g_opt.bcast && !g_opt.gate_out &&
-      !g_cat2.dx2 && !rows__.rows) {
-    // dX of a grouped big-M fp32 GEMM on the bound images of the groups' W^T (k_lin3, blockIdx.y = group)
-    int64_t spacing = 0;
-    if (const void* img = w3_lookup_grouped(weight, N, K, groups, true, &spacing)) {
-      L32Args w{};
-      w.a = dy; w.amask = y_for_mask; w.out = dx; w.add1 = dx_add1; w.add2 = dx_add2;
-      w.M = M; w.Nout = K; w.Kc = N; w.lda = ldy; w.ldw = N; w.ldo = ldx; w.inv_keep = a.inv_keep;
-      w.w3 = img; w.groups = groups; w.g_a = y_group_stride; w.g_o = x_group_stride; w.g_img = spacing;
-      GtProfScope pk__(GT_PROF_GEMM_KERNEL, "k_lin3[dx]", stream, {M, N, K, x_dtype, y_dtype, compute});
-      w3_launch<true>(y_dtype, x_dtype, stream, w);
-      dx_done = true;
-    }
-  }
-  if (dweight && groups > 1 && g3_eligible(compute, x_dtype, y_dtype, M, N, K, ldx, ldy) && !g_cat2.x2 && !rows__.rows && workspace &&
-      workspace_bytes >= need) {
-    // the groups' weight gradients on the pipelined bf16x6 kernel (k_lin3r_dw, blockIdx.y = group) when their weights are bound
-    int64_t spacing = 0;
-    L32DwArgs d{};
-    d.dy = dy; d.ymask = y_for_mask; d.x = x; d.inv_keep = a.inv_keep;
-    d.M = M; d.N = N; d.K = K; d.ldy = ldy; d.ldx = ldx;
-    d.groups = groups; d.g_y = y_group_stride; d.g_x = x_group_stride;
-    if (w3_lookup_grouped(weight, N, K, groups, false, &spacing) && w3r_dw_ok(y_dtype, x_dtype, d)) {
-      const bool will_fork = (g_dw.active && stream == g_dw.main && (dx || g_opt.fork_dw_only) && !(gt_prof_mask() & GT_PROF_LINEAR));
-      const bool forked = will_fork;
-      if (forked) {
-        (void)hipEventRecord(g_dw.ev_fork, stream);
-        (void)hipStreamWaitEvent(g_dw.side, g_dw.ev_fork, 0);
-      }
-      // (a local: a dX that falls through to the generic kernels below must stay on the caller's stream -- ADVICE r5)
-      hipStream_t dw_stream = forked ? g_dw.side : stream;
-      const int shape = w3r_dw_pick_shape(N, K);
-      const int nkb3 = (int)gt_cdiv(K, w3r_dw_xt(shape)), nnb3 = (int)gt_cdiv(N, w3r_dw_zt(shape));
-      int s3 = w3_dw_splits(M, nkb3 * nnb3 * groups);
-      const int cap = w32_dw_splits(M, (int)gt_cdiv(K, 64), (int)gt_cdiv(gt_cdiv(N, 16), w32_pick_nt(N)), false);   // a group's share of the workspace holds this many partial copies
-      if (s3 > cap) s3 = cap;
-      const int64_t per = (int64_t)s3 * (N * K + N);
-      // (reduced right behind the GEMM, not deferred to the end of the backward: the PNA driver gathers the image gradients before that)
-      const bool deferred = false;
-      float* base = reinterpret_cast<float*>(workspace);
-      d.g_part = deferred ? per : a.g_part;
-      d.part = base; d.dbpart = dbias ? base + (int64_t)s3 * N * K : nullptr;
-      d.splits = s3; d.nkb = nkb3; d.nnb = nnb3;
-      d.m_per_split = gt_cdiv(gt_cdiv(M, s3), 32) * 32;
-      dim3 grid3((unsigned)(gt_cdiv(s3, 8) * 8 * nkb3 * nnb3), (unsigned)groups);
-      {
-        {   // (the bracket holds the GEMM kernel alone: one rocprofv3 row; its fixed-order reduce is k_split_reduce's row)
-          GtProfScope pk__(GT_PROF_GEMM_KERNEL, "k_lin3r_dw", dw_stream, {M, N, K, x_dtype, y_dtype, compute});
-          w3r_launch_dw(grid3, dw_stream, d, shape);
-        }
-        if (deferred) {
-          for (int g = 0; g < groups; ++g)
-            (void)gt_defer_push(base + g * per, s3, N * K, N * K, dweight + (int64_t)g * N * K, dbias ? base + g * per + (int64_t)s3 * N * K : nullptr,
-                                dbias ? N : 0, dbias ? N : 0, dbias ? dbias + (int64_t)g * N : nullptr);
-        } else {
-          const int64_t len = N * K, len2 = dbias ? N : 0;
-          const int rg = (int)(gt_cdiv(len + len2, 256) < 2048 ? gt_cdiv(len + len2, 256) : 2048);
-          hipLaunchKernelGGL(k_split_reduce, dim3(rg, groups), dim3(256), 0, dw_stream, (const float*)base, s3, len, dweight, (const float*)d.dbpart,
-                             len2, dbias, d.g_part);
-        }
-      }
-      if (forked) dw_forked(workspace, workspace_bytes);
-      dweight = nullptr; dbias = nullptr;   // done
-      if (!dx || dx_done) { GT_CHECK_LAUNCH(); return GT_OK; }
-    }
-  }
-  if (w32_eligible(compute, x_dtype, M, groups)) {
-    if (!workspace || workspace_bytes < need) {
-      gt_set_error("gt_linear_bwd: workspace too small (%zu < %zu)", workspace_bytes, need);
-      return GT_ERR_WORKSPACE;
-    }
-    const int nt = w32_pick_nt(N);
-    const int nkb = (int)gt_cdiv(K, 64), nnb = (int)gt_cdiv(gt_cdiv(N, 16), nt);
-    const bool will_fork = (g_dw.active && stream == g_dw.main && (dx || g_opt.fork_dw_only) && dweight && !(gt_prof_mask() & GT_PROF_LINEAR));
-    const int splits = w32_dw_splits(M, nkb, nnb, will_fork && !g_dw.urgent);
-    float* part = reinterpret_cast<float*>(workspace);
-    float* wt = part + (size_t)w32_dw_splits(M, nkb, nnb, false) * (size_t)(N * K + N) + 64;   // behind the larger partial area
-    wt = reinterpret_cast<float*>(((uintptr_t)wt + 255) & ~(uintptr_t)255);
-    if (dx) {   // dX = dZ (W^T)^T: the forward-form kernel on the transposed weight
-      // W^T lives in the caller's workspace: a previous call's dW GEMM may still be running on the overlap stream with
-      // its partials in the same workspace (callers hand ONE workspace to consecutive GEMMs, e.g. the four of an encoder
-      // layer) -> wait for the forks that used this range (those on other workspaces keep running).
-      const void* w3t = (y_dtype != GT_F32 && N % 8) ? nullptr : w3_lookup(weight, N, K, true);
-      if (w3t && g_opt.bns.part && !bns_on_rows_kernel(x_dtype, y_dtype, weight, M, N, K, ldx, ldy)) w3t = nullptr;   // the exact kernel's epilogue then
-      if (w3t) {
-        wt = nullptr;   // the bound image of W^T: k_lin3, no transpose
-      } else if (g_opt.weight_t) {
-        wt = const_cast<float*>(g_opt.weight_t);   // read only
-      } else {
-        if (g_dw.active && stream == g_dw.main) dw_release(workspace, workspace_bytes);
-        hipLaunchKernelGGL(k_transpose32, dim3((unsigned)gt_cdiv(K, 32), (unsigned)gt_cdiv(N, 32)), dim3(256), 0, stream, weight, wt, N, K);
-      }
-      L32Args w{};
-      w.a = dy; w.amask = y_for_mask; w.w = wt; w.out = dx; w.add1 = dx_add1; w.add2 = dx_add2;
-      w.M = M; w.Nout = K; w.Kc = N; w.lda = ldy; w.ldw = N; w.ldo = ldx; w.inv_keep = a.inv_keep;
-      if (g_opt.bns.part && x_dtype == GT_F32 && y_dtype == GT_F32) {
-        const BnStatsReq& q = g_opt.bns;
-        w.bn_x = q.x; w.bn_ldx = q.ldx; w.bn_mean = q.mean; w.bn_rstd = q.rstd; w.bn_w = q.w; w.bn_b = q.b;
-        w.bn_relu = q.relu; w.bn_part = q.part;
-      }
-      w.w3 = w3t;
-      if (g_opt.bcast) {
-        w.add_bc = g_opt.bcast; w.add_bidx = g_opt.bcast_idx;
-        if (!w3t || !w3r_ok(y_dtype, x_dtype, w)) { gt_set_error("gt_linear_bwd_bcast: this call does not run on the register-row kernel (ask gt_linear_bwd_bcast_ok)"); return GT_ERR_UNSUPPORTED; }
-      }
-      if (rows__.rows) {
-        if (!w3t) { gt_set_error("gt_linear_set_rows: needs the bound image of W^T"); return GT_ERR_UNSUPPORTED; }
-        w.a_rows = rows__.rows;
-      }
-      if (g_cat2.dx2) {
-        if (!w3t || dx_add1 || dx_add2) { gt_set_error("gt_linear_bwd_cat2: needs a bound weight image and no addends"); return GT_ERR_UNSUPPORTED; }
-        w.out2 = g_cat2.dx2; w.out_split = g_cat2.split; w.ldo2 = g_cat2.ld2;
-      }
-      const bool on_rows_kernel = w3t && w3r_ok(y_dtype, x_dtype, w);
-      GtProfScope pk__(GT_PROF_GEMM_KERNEL, on_rows_kernel ? "k_lin3r[dx]" : (w3t ? "k_lin3[dx]" : "k_lin32[dx]"), stream, {M, N, K, x_dtype, y_dtype, compute});
-      if (on_rows_kernel) w3r_launch(stream, w);
-      else if (w3t) w3_launch<true>(y_dtype, x_dtype, stream, w);
-      else w32_launch<true>(y_dtype, x_dtype, stream, w);
-    }
-    if (dweight) {
-      const bool forked = will_fork;
-      if (forked) {
-        (void)hipEventRecord(g_dw.ev_fork, stream);
-        (void)hipStreamWaitEvent(g_dw.side, g_dw.ev_fork, 0);
-        stream = g_dw.side;
-      }
-      L32DwArgs d{};
-      d.dy = dy; d.ymask = y_for_mask; d.x = x; d.inv_keep = a.inv_keep;
-      d.M = M; d.N = N; d.K = K; d.ldy = ldy; d.ldx = ldx;
-      if (g_cat2.x2) { d.x2 = g_cat2.x2; d.x_split = g_cat2.split; d.ldx2 = g_cat2.ld2; }
-      // weights with bound images run the bf16x6 dW kernel too (160 x 160 output tiles, split over M; linear3x.h)
-      const bool split3 = x_dtype == GT_F32 && w3_lookup(weight, N, K, false) != nullptr && (y_dtype == GT_F32 || N % 8 == 0);
-      if (rows__.rows && !split3) { gt_set_error("gt_linear_set_rows: needs the bound weight image"); return GT_ERR_UNSUPPORTED; }
-      d.dy_rows = rows__.rows;
-      if (split3) {
-        const int nkb3 = (int)gt_cdiv(K, W3D_T), nnb3 = (int)gt_cdiv(N, W3D_T);
-        int s3 = w3_dw_splits(M, nkb3 * nnb3);
-        const int cap = w32_dw_splits(M, nkb, nnb, false);   // the workspace is sized for this many partial copies
-        if (s3 > cap) s3 = cap;
-        bool deferred;
-        float* part3 = dw_part(part, s3, N, K, &deferred);
-        d.part = part3; d.dbpart = dbias ? part3 + (size_t)s3 * N * K : nullptr;
-        d.splits = s3; d.nkb = nkb3; d.nnb = nnb3;
-        d.m_per_split = gt_cdiv(gt_cdiv(M, s3), 32) * 32;
-        dim3 grid3((unsigned)(gt_cdiv(s3, 8) * 8 * nkb3 * nnb3));
-        {
-          const bool pipelined = w3r_dw_ok(y_dtype, x_dtype, d);
-          {
-            GtProfScope pk__(GT_PROF_GEMM_KERNEL, pipelined ? "k_lin3r_dw" : "k_lin3_dw", stream, {M, N, K, x_dtype, y_dtype, compute});
-            if (pipelined) w3r_launch_dw(grid3, stream, d);   // stages pipelined (linear3r.h)
-            else if (y_dtype == GT_F32) w3_launch_dw<float, float>(grid3, stream, d);
-            else w3_launch_dw<gt_bf16, float>(grid3, stream, d);
-          }
-          dw_reduce(stream, deferred, part3, s3, N * K, dweight, d.dbpart, dbias ? N : 0, dbias);
-        }
-        if (forked) dw_forked(workspace, workspace_bytes);
-        GT_CHECK_LAUNCH();
-        return GT_OK;
-      }
-      bool deferred;
-      float* part2w = dw_part(part, splits, N, K, &deferred);
-      d.part = part2w; d.dbpart = dbias ? part2w + (size_t)splits * N * K : nullptr;
-      d.splits = splits; d.nkb = nkb; d.nnb = nnb;
-      d.m_per_split = gt_cdiv(gt_cdiv(M, splits), 16) * 16;
-      dim3 grid((unsigned)(gt_cdiv(splits, 8) * 8 * nkb * nnb));
-      {
-        {
-          GtProfScope pk__(GT_PROF_GEMM_KERNEL, "k_lin32_dw", stream, {M, N, K, x_dtype, y_dtype, compute});
-          if (y_dtype == GT_F32) w32_launch_dw_nt<float, float>(nt, grid, stream, d);
-          else w32_launch_dw_nt<gt_bf16, float>(nt, grid, stream, d);
-        }
-        dw_reduce(stream, deferred, part2w, splits, N * K, dweight, d.dbpart, dbias ? N : 0, dbias);
-      }
-      if (forked) dw_forked(workspace, workspace_bytes);
-    }
-    GT_CHECK_LAUNCH();
-    return GT_OK;
-  }
-  if (dx && x_dtype == GT_BF16 && y_dtype == GT_BF16 && compute == GT_BF16 && groups == 1 && M >= W1_MIN_M && (!y_for_mask || g_opt.gate_out)) {
-    // dX = dY W on the bound image of W^T (linear1.h); a gate here applies to the OUTPUT columns (gt_linear_bwd_gate_out)
-    if (const void* img = w1_lookup(weight, N, K, true)) {
-      L1Args l{};
-      l.a = (const gt_bf16*)dy; l.img = (const unsigned char*)img; l.out = (gt_bf16*)dx;
-      l.gate = g_opt.gate_out ? (const gt_bf16*)y_for_mask : nullptr; l.gate_inv_keep = a.inv_keep;
-      l.add1 = (const gt_bf16*)dx_add1; l.add2 = (const gt_bf16*)dx_add2;
-      l.M = M; l.lda = ldy; l.ldo = ldx; l.N = (int)K; l.K = (int)N;
-      const bool ring = w2_take(l, w1_pick_ntw(K, N) != 0);
-      {
-        GtProfScope pk__(GT_PROF_GEMM_KERNEL, ring ? "k_lin2[dx]" : "k_lin1[dx]", stream, {M, N, K, x_dtype, y_dtype, compute});
-        dx_done = ring ? w2_launch(stream, l) : w1_launch(stream, l);
-      }
-    }
-  }
-  if (g_opt.gate_out) {
-    if (dx && !dx_done) { gt_set_error("gt_linear_bwd_gate_out: not covered (ask gt_linear_bwd_gate_out_ok)"); return GT_ERR_UNSUPPORTED; }
-    a.ymask = nullptr;   // the gate belongs to the dX output, not to dY: the weight gradient below reads dY as it is
-    y_for_mask = nullptr;
-  }
-  // (shape matching alone must not route a general GEMM with per-call options here: k_heads_dx knows none of them)
-  if (dx && !dx_done && !y_for_mask && !g_opt.mul_mask && !g_opt.bns.part && !g_opt.gate_out && dropout_p == 0.f &&
-      heads_shape_ok(x_dtype, y_dtype, M, N, K, ldx, ldy, groups) && workspace &&
-      workspace_bytes >= heads_dx_workspace_bytes(M, N)) {   // the prediction heads: the contraction is their 25 010 columns (linear_heads.h)
-    HeadsArgs h{};
-    h.w = weight; h.dy = (const float*)dy; h.M = M; h.N = N; h.ldx = ldx; h.ldy = ldy;
-    GtProfScope pk__(GT_PROF_GEMM_KERNEL, "k_heads_dx+reduce", stream, {M, N, K, x_dtype, y_dtype, compute});
-    heads_launch_dx(compute, stream, h, workspace, (float*)dx, (const float*)dx_add1, (const float*)dx_add2);
-    dx_done = true;
-  }
-  if (dx && !dx_done) {
-    const int bm = pick_bm(M);
-    // split-N partials are plain fp32 sums: only for fp32 dX without fused addends (and not for grouped launches)
-    int splits = (x_dtype == GT_F32 && !dx_add1 && !dx_add2 && ldx == K && groups == 1) ? dx_splits(M, N, K, bm) : 1;
-    if (splits > 1 && (!workspace || workspace_bytes < need)) splits = 1;
-    a.splits = splits;
-    a.n_per_split = gt_cdiv(gt_cdiv(N, splits), 64) * 64;
-    a.out = splits > 1 ? workspace : dx;
-    a.ntiles = (int)gt_cdiv(K, BN);
-    dim3 grid((unsigned)(gt_cdiv(gt_cdiv(M, bm), 8) * 8 * a.ntiles), (unsigned)groups, (unsigned)splits);
-    const int t0 = y_dtype, t1 = x_dtype;
-    GtProfScope pk__(GT_PROF_GEMM_KERNEL, "k_linear_dx", stream, {M, N, K, x_dtype, y_dtype, compute});
-    if (bm == 64) GT_LIN_DISPATCH_BM(k_linear_dx, 64, grid, a);
-    else GT_LIN_DISPATCH_BM(k_linear_dx, 128, grid, a);
-    if (splits > 1) {
-      const int64_t len = M * K;
-      const int rg = (int)(gt_cdiv(len, 256) < 2048 ? gt_cdiv(len, 256) : 2048);
-      hipLaunchKernelGGL(k_split_reduce, dim3(rg), dim3(256), 0, stream, (const float*)workspace, splits, len,
-                         reinterpret_cast<float*>(dx), (const float*)nullptr, (int64_t)0, (float*)nullptr, (int64_t)0);
-    }
-  }
-  if (dweight && small_wide_ok(x_dtype, y_dtype, M, K, ldx, ldy, groups)) {   // wide short-M GEMM: dW on the one-wave-per-tile kernel
-    const bool forked = g_dw.active && stream == g_dw.main && (dx || g_opt.fork_dw_only) && a.splits <= 1 && workspace && workspace_bytes &&
-                        !(gt_prof_mask() & GT_PROF_LINEAR);
-    if (forked) {
-      (void)hipEventRecord(g_dw.ev_fork, stream);
-      (void)hipStreamWaitEvent(g_dw.side, g_dw.ev_fork, 0);
-      stream = g_dw.side;
-    }
-    SmallArgs sa{};
-    sa.x = (const float*)x; sa.w = weight; sa.dy = (const float*)dy; sa.ymask = (const float*)y_for_mask;
-    sa.M = M; sa.N = N; sa.K = K; sa.ldx = ldx; sa.ldy = ldy; sa.inv_keep = a.inv_keep;
-    sa.out = dweight; sa.db = dbias;
-    {
-      GtProfScope pk__(GT_PROF_GEMM_KERNEL, "k_small_dw", stream, {M, N, K, x_dtype, y_dtype, compute});
-      small_launch(SMALL_DW, compute, gt_cdiv(N, 32) * gt_cdiv(K, 16), M, stream, sa);
-    }
-    if (forked) dw_forked(workspace, workspace_bytes);
-    GT_CHECK_LAUNCH();
-    return GT_OK;
-  }
-  if (dweight) {
-    const int splits = dw_splits(M, N, K, compute);
-    if (!workspace || workspace_bytes < need) {
-      gt_set_error("gt_linear_bwd: workspace too small (%zu < %zu)", workspace_bytes, need);
-      return GT_ERR_WORKSPACE;
-    }
-    // dW is off the critical path of the backward (only the optimizer reads it): inside a
-    // gt_overlap_dw_begin/_end section it runs on the side stream beside dX and whatever follows.
-    // (not while the launch profiler brackets this call: its events sit on the caller's stream only)
-    bool forked = false;
-    if (g_dw.active && stream == g_dw.main && (dx || g_opt.fork_dw_only) && a.splits <= 1 && !(gt_prof_mask() & GT_PROF_LINEAR)) {
-      (void)hipEventRecord(g_dw.ev_fork, stream);
-      (void)hipStreamWaitEvent(g_dw.side, g_dw.ev_fork, 0);
-      stream = g_dw.side;
-      forked = true;
-    }
-    if (dw16_ok(x_dtype, y_dtype, compute, x, dy, a.ymask, M, N, K, ldx, ldy, groups)) {   // bf16 token rows: the LDS-DMA ring kernel (linear_dw16.h)
-      Dw16Args d{};
-      d.dy = (const gt_bf16*)dy; d.x = (const gt_bf16*)x; d.M = M; d.N = N; d.K = K; d.ldy = ldy; d.ldx = ldx;
-      d.splits = dw16_splits(M, N, K, splits);
-      d.m_per_split = gt_cdiv(gt_cdiv(M, d.splits), D16_ROWS) * D16_ROWS;
-      bool deferred;
-      d.part = dw_part(reinterpret_cast<float*>(workspace), d.splits, N, K, &deferred);
-      d.dbpart = dbias ? d.part + (size_t)d.splits * N * K : nullptr;
-      d.ntx = (int)(N / D16_T);
-      d.ntiles = d.ntx * (int)(K / D16_T);
-      {
-        {
-          GtProfScope pk__(GT_PROF_GEMM_KERNEL, "k_dw16", stream, {M, N, K, x_dtype, y_dtype, compute});
-          hipLaunchKernelGGL(k_dw16, dim3((unsigned)(gt_cdiv(d.splits, 8) * 8 * d.ntiles)), dim3(256), 0, stream, d);
-        }
-        dw_reduce(stream, deferred, d.part, d.splits, N * K, dweight, d.dbpart, dbias ? N : 0, dbias);
-      }
-      if (forked) dw_forked(workspace, workspace_bytes);
-      GT_CHECK_LAUNCH();
-      return GT_OK;
-    }
-    const int64_t bmc = compute == GT_BF16 ? 64 : 32;
-    a.splits = splits;
-    a.m_per_split = gt_cdiv(gt_cdiv(M, splits), bmc) * bmc;
-    a.out = workspace;
-    a.dbpart = dbias ? reinterpret_cast<float*>(workspace) + (size_t)splits * N * K : nullptr;
-    a.ntx = (int)gt_cdiv(N, BN);
-    a.ntiles = a.ntx * (int)gt_cdiv(K, BN);
-    dim3 grid((unsigned)(gt_cdiv(splits, 8) * 8 * a.ntiles), (unsigned)groups);
-    const int t0 = y_dtype, t1 = x_dtype;
-    {
-      {
-        GtProfScope pk__(GT_PROF_GEMM_KERNEL, "k_linear_dw", stream, {M, N, K, x_dtype, y_dtype, compute});
-        GT_LIN_DISPATCH(k_linear_dw, grid, a);
-      }
-      const int64_t len = N * K, len2 = dbias ? N : 0;
-      int rg = (int)(gt_cdiv(len + len2, 256) < 2048 ? gt_cdiv(len + len2, 256) : 2048);
-      hipLaunchKernelGGL(k_split_reduce, dim3(rg, groups), dim3(256), 0, stream, (const float*)workspace, splits, len, dweight,
-                         (const float*)a.dbpart, len2, dbias, a.g_part);
-    }
-    if (forked) dw_forked(workspace, workspace_bytes);
-  }
-  GT_CHECK_LAUNCH();
-  return GT_OK;
+  LinBwd c{x_dtype, y_dtype, compute, x, weight, dy, gmul, dx_add1, dx_add2, dx, dweight, dbias, M, N, K, ldx, ldy, 1, 0, 0, 0.f, workspace,
+               workspace_bytes, (hipStream_t)stream_};
+  take_bwd(c);
+  c.mul_mask = true;
+  return lin_bwd(c);
 }
 
 // ---- JK = "cat" without the copy: X = [X1 | X2] (modules/gnn_module.py:104-105 feeding models/gnn_transformer.py:92) -------------
@@ -1660,41 +1643,40 @@ extern "C" int gt_linear_rows_ok(int compute, int x_dtype, int y_dtype, const fl
   return (rows_eligible(compute, x_dtype, y_dtype, weight, M, N, K)) ? 1 : 0;
 }
 extern "C" int gt_linear_set_rows(const int32_t* rows) {
-  g_rows = rows;
+  g_pending.map.rows = rows;
   return GT_OK;
 }
 // ... and LayerNorm(ln_w, ln_b, eps) of every stored row in the same epilogue (forward only): ln_out (storage type and pitch of y) gets
 // the normalised row, ln_mean / ln_rstd its statistics, all at the row the output goes to.  N must fill one column block of the kernel.
 extern "C" int gt_linear_rows_layernorm_ok(int64_t N) { return (N > 0 && N % 16 == 0 && (int64_t)w3_pick_nt(N) * 16 == N) ? 1 : 0; }
-extern "C" int gt_linear_set_rows_layernorm(const int32_t* rows, const float* ln_w, const float* ln_b, float eps, void* ln_out,
-                                            float* ln_mean, float* ln_rstd) {
+extern "C" int gt_linear_set_rows_layernorm(const int32_t* rows, const float* ln_w, const float* ln_b, float eps, void* ln_out, float* ln_mean,
+                                            float* ln_rstd) {
   GT_CHECK_ARG(rows && ln_w && ln_b && ln_out && ln_mean && ln_rstd, "null buffer");
-  g_rows = rows;
-  g_rows_ln.w = ln_w; g_rows_ln.b = ln_b; g_rows_ln.out = ln_out; g_rows_ln.mean = ln_mean; g_rows_ln.rstd = ln_rstd; g_rows_ln.eps = eps;
+  g_pending.map = LinRowMap{rows, ln_w, ln_b, ln_out, ln_mean, ln_rstd, eps};
   return GT_OK;
 }
 // Y[M][N] = [X1 | X2] W^T + b with X1 [M][K1] (pitch ldx1), X2 [M][K2] (pitch ldx2), W [N][K1 + K2]; fp32 rows, y_dtype fp32 / bf16
-extern "C" int gt_linear_fwd_cat2(int y_dtype, int compute, const void* x1, int64_t K1, int64_t ldx1, const void* x2, int64_t K2,
-                                  int64_t ldx2, const float* weight, const float* bias, void* y, int64_t M, int64_t N, int64_t ldy,
-                                  gt_stream_t stream_) {
-  RowsClear rows_clear__;
+extern "C" int gt_linear_fwd_cat2(int y_dtype, int compute, const void* x1, int64_t K1, int64_t ldx1, const void* x2, int64_t K2, int64_t ldx2,
+                                  const float* weight, const float* bias, void* y, int64_t M, int64_t N, int64_t ldy, gt_stream_t stream_) {
+  LinFwd f{GT_F32, y_dtype, compute, x1, weight, bias, y, M, N, K1 + K2, ldx1, ldy, 1, 0, 0, 0, 0.f, 0, (hipStream_t)stream_};
+  f.map = take_map();   // (dropped even when the check below refuses the call)
   GT_CHECK_ARG(x1 && x2 && K1 > 0 && K2 > 0 && K1 % 4 == 0 && K2 % 4 == 0 && ldx2 >= K2 && ldx2 % 4 == 0, "bad second operand");
-  Cat2Scope scope__;
-  g_cat2.x2 = x2; g_cat2.split = K1; g_cat2.ld2 = ldx2;
-  return linear_fwd_impl(GT_F32, y_dtype, compute, x1, weight, bias, y, nullptr, M, N, K1 + K2, ldx1, ldy, 1, 0, 0, 0, 0.f, 0, stream_);
+  f.x2 = x2; f.x_split = K1; f.ldx2 = ldx2;
+  return lin_fwd(f);
 }
 // backward of the above: dX1 [M][K1] (pitch lddx1) and dX2 [M][K2] (pitch lddx2) from dY [M][N] (y_dtype, pitch ldy); dW [N][K1+K2], db
-extern "C" int gt_linear_bwd_cat2(int y_dtype, int compute, const void* x1, int64_t K1, int64_t ldx1, const void* x2, int64_t K2,
-                                  int64_t ldx2, const float* weight, const void* dy, void* dx1, int64_t lddx1, void* dx2, int64_t lddx2,
-                                  float* dweight, float* dbias, int64_t M, int64_t N, int64_t ldy, void* workspace,
-                                  size_t workspace_bytes, gt_stream_t stream_) {
-  RowsClear rows_clear__;
+extern "C" int gt_linear_bwd_cat2(int y_dtype, int compute, const void* x1, int64_t K1, int64_t ldx1, const void* x2, int64_t K2, int64_t ldx2,
+                                  const float* weight, const void* dy, void* dx1, int64_t lddx1, void* dx2, int64_t lddx2, float* dweight,
+                                  float* dbias, int64_t M, int64_t N, int64_t ldy, void* workspace, size_t workspace_bytes, gt_stream_t stream_) {
+  const LinRowMap map = take_map();   // (dropped even when the checks below refuse the call)
   GT_CHECK_ARG(x1 && x2 && dx1 && dx2 && K1 > 0 && K2 > 0 && K1 % 4 == 0 && K2 % 4 == 0, "bad operands");
   GT_CHECK_ARG(ldx1 == lddx1 && ldx2 == lddx2, "dX pitches must equal the X pitches");   // (one pitch per matrix in the kernel arguments)
-  Cat2Scope scope__;
-  g_cat2.x2 = x2; g_cat2.dx2 = dx2; g_cat2.split = K1; g_cat2.ld2 = ldx2;
-  return gt_linear_bwd_grouped(GT_F32, y_dtype, compute, x1, weight, dy, nullptr, nullptr, nullptr, dx1, dweight, dbias, M, N, K1 + K2,
-                               ldx1, ldy, 1, 0, 0, 0.f, workspace, workspace_bytes, stream_);
+  LinBwd c{GT_F32, y_dtype, compute, x1, weight, dy, nullptr, nullptr, nullptr, dx1, dweight, dbias, M, N, K1 + K2, ldx1, ldy, 1, 0, 0, 0.f,
+           workspace, workspace_bytes, (hipStream_t)stream_};
+  take_bwd(c);
+  c.map = map;
+  c.x2 = x2; c.dx2 = dx2; c.x_split = K1; c.ldx2 = ldx2;
+  return lin_bwd(c);
 }
 
 // ---- bf16x3 weight images (linear3x.h) --------------------------------------------------------------------------------
@@ -1789,9 +1771,7 @@ extern "C" int gt_w1_unbind(void) {
   g_w1.n = 0;
   return GT_OK;
 }
-// gt_linear_bwd_ld2 whose gate (`y_or_mul` [M][ldx]: the forward output of the layer BELOW when dropout_p >= 0 -- dZ = dX * 1[y > 0]
-// / (1 - p) -- or, with dropout_p < 0, a saved multiplier) applies to the dX OUTPUT of this call; dY is used as it is (also by the
-// weight gradient).  Only on the weight-stationary path: ask gt_linear_bwd_gate_out_ok first.
+// the gate (dropout_p >= 0: the forward output of the layer BELOW; < 0: a saved multiplier) applies to the dX OUTPUT, dY is used as it is
 extern "C" int gt_linear_bwd_gate_out_ok(int x_dtype, int y_dtype, int compute, const float* weight, int64_t M, int64_t N, int64_t K) {
   return (x_dtype == GT_BF16 && y_dtype == GT_BF16 && compute == GT_BF16 && M >= W1_MIN_M && w1_lookup(weight, N, K, true) &&
           w1_pick_ntw(K, N)) ? 1 : 0;
@@ -1801,10 +1781,12 @@ extern "C" int gt_linear_bwd_gate_out(int x_dtype, int y_dtype, int compute, con
                                       float* dbias, int64_t M, int64_t N, int64_t K, int64_t ldx, int64_t ldy, float dropout_p,
                                       void* workspace, size_t workspace_bytes, gt_stream_t stream_) {
   GT_CHECK_ARG(y_or_mul && dx, "gt_linear_bwd_gate_out needs the gate tensor and dx");
-  g_opt.gate_out = true;
-  g_opt.mul_mask = dropout_p < 0.f;
-  return gt_linear_bwd_grouped(x_dtype, y_dtype, compute, x, weight, dy, y_or_mul, dx_add1, dx_add2, dx, dweight, dbias, M, N, K, ldx, ldy,
-                               1, 0, 0, dropout_p < 0.f ? 0.f : dropout_p, workspace, workspace_bytes, stream_);
+  LinBwd c{x_dtype, y_dtype, compute, x, weight, dy, y_or_mul, dx_add1, dx_add2, dx, dweight, dbias, M, N, K, ldx, ldy, 1, 0, 0,
+               dropout_p < 0.f ? 0.f : dropout_p, workspace, workspace_bytes, (hipStream_t)stream_};
+  take_bwd(c);
+  c.gate_out = true;
+  c.mul_mask = dropout_p < 0.f;
+  return lin_bwd(c);
 }
 
 // y = LayerNorm(resid + dropout(a)) * ln_w + ln_b with a = x W^T + b, as ONE launch: the GEMM's epilogue holds whole rows (N = the

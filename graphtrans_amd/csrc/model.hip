@@ -13,6 +13,7 @@
 #include <vector>
 
 #include "gt_common.h"
+#include "linear_call.h"
 
 namespace {
 
@@ -731,22 +732,25 @@ extern "C" int gt_model_forward(const gt_model* m, void* ctx_, void* arena, floa
   void* g2t_out = P(c->o_hn);
   // ... and norm_input (transformer_encoder.py:53-57) in the same epilogue when a token row fills one column block of the kernel
   const bool fuse_nin = c->fuse_rows && m->nin_w && gt_linear_rows_layernorm_ok(d);
+  LinRowMap map{};   // rides, like the second operand below, in the GEMM call's record
   if (c->fuse_rows) {
     int32_t* rmap = (int32_t*)P(c->o_rowmap);
     if (fuse_nin) {
       float* st0 = (float*)P(c->o_st0);
       GT_TRY(gt_seq_token_rows_layernorm(tdt, m->cls, graph_ptr, node_graph, c->seq_desc, B, 1, m->with_cls ? 1 : 0, N, d, P(c->o_tok), rmap, m->nin_w,
                                          m->nin_b, m->nin_eps, P(c->o_xin), st0, st0 + rows, st));
-      GT_TRY(gt_linear_set_rows_layernorm(rmap, m->nin_w, m->nin_b, m->nin_eps, P(c->o_xin), st0, st0 + rows));
+      map = LinRowMap{rmap, m->nin_w, m->nin_b, P(c->o_xin), st0, st0 + rows, m->nin_eps};
     } else {
       GT_TRY(gt_seq_token_rows(tdt, m->cls, graph_ptr, node_graph, c->seq_desc, B, 1, m->with_cls ? 1 : 0, N, d, P(c->o_tok), rmap, st));
-      GT_TRY(gt_linear_set_rows(rmap));
+      map.rows = rmap;
     }
     g2t_out = P(c->o_tok);
   }
+  LinFwd g2t{};
   if (c->cat2) {
     c->node_rep = nullptr;
-    GT_TRY(gt_linear_fwd_cat2(tdt, compute, c->first, D, D, c->h_last, D, D, m->g2t_w, m->g2t_b, g2t_out, N, d, d, st));
+    g2t = LinFwd{GT_F32, tdt, compute, c->first, m->g2t_w, m->g2t_b, g2t_out, N, d, 2 * D, D, d, 1, 0, 0, 0, 0.f, 0, (hipStream_t)st};
+    g2t.x2 = c->h_last; g2t.x_split = D; g2t.ldx2 = D;
   } else {
     if (m->jk_cat) {   // torch.cat([h_list[0], h_list[-1]], 1)   (gnn_module.py:104-105)
       GT_TRY(gt_copy2d(P(c->o_cat), c->Kc * 4, c->first, D * 4, D * 4, N, st));
@@ -755,8 +759,10 @@ extern "C" int gt_model_forward(const gt_model* m, void* ctx_, void* arena, floa
     } else {
       c->node_rep = c->h_last;
     }
-    GT_TRY(gt_linear_fwd(GT_F32, tdt, compute, c->node_rep, m->g2t_w, m->g2t_b, g2t_out, N, d, c->Kc, 0, 0.f, 0, st));
+    g2t = LinFwd{GT_F32, tdt, compute, c->node_rep, m->g2t_w, m->g2t_b, g2t_out, N, d, c->Kc, c->Kc, d, 1, 0, 0, 0, 0.f, 0, (hipStream_t)st};
   }
+  g2t.map = map;
+  GT_TRY(lin_fwd(g2t));
   if (!c->fuse_rows)
     GT_TRY(gt_seq_gather_cls32(tdt, P(c->o_hn), m->cls, graph_ptr, c->seq_desc, B, 1, c->max_npos, m->with_cls ? 1 : 0, d, P(c->o_tok), st));
   const void* cur = P(c->o_tok);
@@ -888,9 +894,11 @@ extern "C" int gt_model_backward(const gt_model* m, void* ctx_, const float* dlo
     }
     // ---- token rows -> node rows (+ the CLS gradient)
     const void* d_hn = Q(c->q_d_hn);
+    LinBwd g2t{};
+    const int32_t* rmap = nullptr;
     if (c->fuse_rows) {   // the GEMMs read the token-row gradient through the row map; the cls gradient = column sums of the CLS rows
       if (m->cls) GT_TRY(gt_colsum_rows_f32(tdt, dcur, c->last_rows, B, d, G + m->off_cls, st));
-      GT_TRY(gt_linear_set_rows((const int32_t*)P(c->o_rowmap)));
+      rmap = (const int32_t*)P(c->o_rowmap);
       d_hn = dcur;
     } else {
       GT_TRY(gt_seq_scatter(tdt, dcur, nullptr, c->graph_ptr, c->node_graph, c->seq_desc, B, 1, m->with_cls ? 1 : 0, N, d, Q(c->q_d_hn),
@@ -899,15 +907,19 @@ extern "C" int gt_model_backward(const gt_model* m, void* ctx_, const float* dlo
     }
     if (c->g2t_wt && m->st_dw) GT_TRY(gt_stream_wait_event(st, m->ev_wt[1]));   // W^T was written on the overlap stream beside the forward
     if (c->cat2) {   // d h_list[0] -> dJ, d h_list[-1] -> dA straight from the GEMM
-      GT_TRY(gt_linear_bwd_cat2(tdt, compute, c->first, D, D, c->h_last, D, D, m->g2t_w, d_hn, Q(c->q_dJ), D, Q(c->q_dA), D,
-                                G + m->off_g2t_w, G + m->off_g2t_b, N, d, d, W(), ws_bytes, st));
+      g2t = LinBwd{GT_F32, tdt, compute, c->first, m->g2t_w, d_hn, nullptr, nullptr, nullptr, Q(c->q_dJ), G + m->off_g2t_w, G + m->off_g2t_b,
+                   N, d, 2 * D, D, d, 1, 0, 0, 0.f, W(), ws_bytes, (hipStream_t)st};
+      g2t.x2 = c->h_last; g2t.dx2 = Q(c->q_dA); g2t.x_split = D; g2t.ldx2 = D;
       c->dy = Q(c->q_dA);
     } else {
-      GT_TRY(gt_linear_bwd_wt(GT_F32, tdt, compute, c->node_rep, m->g2t_w, c->g2t_wt, d_hn, nullptr, nullptr, nullptr, Q(c->q_d_rep),
-                              G + m->off_g2t_w, G + m->off_g2t_b, N, d, Kc, 0.f, W(), ws_bytes, st));
+      g2t = LinBwd{GT_F32, tdt, compute, c->node_rep, m->g2t_w, d_hn, nullptr, nullptr, nullptr, Q(c->q_d_rep), G + m->off_g2t_w,
+                   G + m->off_g2t_b, N, d, Kc, Kc, d, 1, 0, 0, 0.f, W(), ws_bytes, (hipStream_t)st};
+      g2t.weight_t = c->g2t_wt;
       if (m->jk_cat) c->dy = nullptr;   // split below (stage 2 prologue)
       else c->dy = Q(c->q_d_rep);
     }
+    g2t.map.rows = rmap;
+    GT_TRY(lin_bwd(g2t));
     GT_TRY(flush());
     c->stages_done |= 1;
   }
