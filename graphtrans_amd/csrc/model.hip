@@ -12,16 +12,10 @@
 #include <cstring>
 #include <vector>
 
-#include "gt_common.h"
+#include "host_seq.h"
 #include "linear_call.h"
 
 namespace {
-
-#define GT_TRY(call)                \
-  do {                              \
-    int rc__ = (call);              \
-    if (rc__ != GT_OK) return rc__; \
-  } while (0)
 
 constexpr int MAXL = GT_MODEL_MAX_LAYERS;
 constexpr int MAXT = GT_MODEL_MAX_TABLES;
@@ -37,7 +31,6 @@ struct Bump {
   }
 };
 inline size_t c4(size_t n) { return (n + 3) / 4 * 4; }
-inline size_t esz(int dtype) { return dtype == GT_BF16 ? 2 : 4; }
 
 // ---- per-forward context (host memory of the caller, opaque to it) -----------------------------------------------------------
 struct Ctx {
@@ -234,7 +227,7 @@ extern "C" int gt_model_prepare(const gt_model* m, const gt_model_batch* b, void
   const int L = m->L, nenc = m->n_enc;
   c->compute = b->compute;
   c->tdt = b->tdt;
-  c->tsz = esz(b->tdt);
+  c->tsz = gt_elt_bytes(b->tdt);
   const size_t tsz = c->tsz;
   const int cls = m->with_cls ? 1 : 0;
 
@@ -272,20 +265,25 @@ extern "C" int gt_model_prepare(const gt_model* m, const gt_model_batch* b, void
 
   // ---- batch descriptors
   const int training = b->training ? 1 : 0;
+  // what the GCN and the GIN descriptor share (the fields carry the same names); g arrives as a copy of the model's static part
+  auto fill_conv = [&](auto& g, int l) {
+    g.N = N; g.E = E; g.B = B;
+    g.has_vn = m->has_vn; g.relu = l != L - 1; g.residual = m->residual;
+    g.training = training; g.compute = c->compute;
+    g.dropout_p = training ? b->gnn_p : 0.f;
+    g.seed = b->gnn_seed + SEED_STEP * (uint64_t)(2 * l + 1);
+    g.edge_attr = (g.edge_mode != GT_EDGE_NONE && E > 0) ? b->edge_attr : nullptr;
+    g.ev_x_ready = nullptr;
+    g.ev_dx_wait = (m->st_vn && m->has_vn && l < L - 1) ? m->ev_extra[l] : nullptr;
+    g.x_has_vn = m->has_vn;
+    g.vn_next = nullptr; g.ev_vn_next = nullptr;
+  };
   for (int l = 0; l < L; ++l) {
     if (m->conv == GT_CONV_GCN) {
       gt_gcn_layer& g = c->gcn[l];
       g = gcn_static(m)[l];
-      g.N = N; g.E = E; g.B = B;
-      g.has_vn = m->has_vn; g.relu = l != L - 1; g.residual = m->residual;
-      g.training = training; g.compute = c->compute;
-      g.dropout_p = training ? b->gnn_p : 0.f;
-      g.seed = b->gnn_seed + SEED_STEP * (uint64_t)(2 * l + 1);
-      g.edge_attr = (g.edge_mode != GT_EDGE_NONE && E > 0) ? b->edge_attr : nullptr;
-      g.ev_x_ready = nullptr;
-      g.ev_dx_wait = (m->st_vn && m->has_vn && l < L - 1) ? m->ev_extra[l] : nullptr;
-      g.x_has_vn = m->has_vn;
-      g.vn_next = nullptr; g.ev_vn_next = nullptr; g.lin_wt = nullptr;
+      fill_conv(g, l);
+      g.lin_wt = nullptr;
       g.prev_saved = nullptr; g.prev_bn_w = g.prev_bn_b = nullptr; g.prev_bn_part = nullptr; g.bn_part_in = nullptr;
       g.prev_relu = 0; g.bn_nparts_in = 0; g.ev_graph_ready = nullptr;
       g.dx_bcast = nullptr; g.dx_bcast_idx = nullptr;
@@ -299,16 +297,8 @@ extern "C" int gt_model_prepare(const gt_model* m, const gt_model_batch* b, void
     } else {
       gt_gin_layer& g = c->gin[l];
       g = gin_static(m)[l];
-      g.N = N; g.E = E; g.B = B;
-      g.has_vn = m->has_vn; g.relu = l != L - 1; g.residual = m->residual;
-      g.training = training; g.compute = c->compute;
-      g.dropout_p = training ? b->gnn_p : 0.f;
-      g.seed = b->gnn_seed + SEED_STEP * (uint64_t)(2 * l + 1);
-      g.edge_attr = (g.edge_mode != GT_EDGE_NONE && E > 0) ? b->edge_attr : nullptr;
-      g.ev_x_ready = nullptr;
-      g.ev_dx_wait = (m->st_vn && m->has_vn && l < L - 1) ? m->ev_extra[l] : nullptr;
-      g.x_has_vn = m->has_vn;
-      g.vn_next = nullptr; g.ev_vn_next = nullptr; g.w1_t = g.w2_t = nullptr;
+      fill_conv(g, l);
+      g.w1_t = g.w2_t = nullptr;
     }
   }
   const int nvn = m->has_vn ? L - 1 : 0;
@@ -589,19 +579,22 @@ extern "C" int gt_model_forward(const gt_model* m, void* ctx_, void* arena, floa
     }
   }
   // ---- graph pointers into the descriptors
+  auto fill_csr = [&](auto& g) {   // every conv descriptor
+    g.in_ptr = in_ptr; g.in_src = in_src; g.in_eid = in_eid; g.out_ptr = out_ptr; g.out_dst = out_dst; g.out_eid = out_eid;
+  };
   for (int l = 0; l < L; ++l) {
     if (m->conv == GT_CONV_GCN) {
       gt_gcn_layer& g = c->gcn[l];
-      g.graph_ptr = graph_ptr; g.node_graph = node_graph; g.in_ptr = in_ptr; g.in_src = in_src; g.in_eid = in_eid;
-      g.out_ptr = out_ptr; g.out_dst = out_dst; g.out_eid = out_eid; g.deg = deg; g.dis = dis;
+      fill_csr(g);
+      g.graph_ptr = graph_ptr; g.node_graph = node_graph; g.deg = deg; g.dis = dis;
     } else if (m->conv == GT_CONV_PNA) {
       gt_pna_layer& g = c->pna[l];
-      g.in_ptr = in_ptr; g.in_src = in_src; g.in_eid = in_eid; g.out_ptr = out_ptr; g.out_dst = out_dst; g.out_eid = out_eid;
+      fill_csr(g);
       g.scales = (const float*)P(c->o_scales);
     } else {
       gt_gin_layer& g = c->gin[l];
-      g.graph_ptr = graph_ptr; g.node_graph = node_graph; g.in_ptr = in_ptr; g.in_src = in_src; g.in_eid = in_eid;
-      g.out_ptr = out_ptr; g.out_dst = out_dst; g.out_eid = out_eid;
+      fill_csr(g);
+      g.graph_ptr = graph_ptr; g.node_graph = node_graph;
     }
   }
   for (int l = 0; l < nvn; ++l) { c->vn[l].graph_ptr = graph_ptr; c->vn[l].node_graph = node_graph; }

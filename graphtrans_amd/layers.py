@@ -120,33 +120,50 @@ def encoder_layer_params(mod):
             mod.linear2.weight, mod.linear2.bias, mod.norm1.weight, mod.norm1.bias, mod.norm2.weight, mod.norm2.bias]
 
 
+ENC_ACT = {"relu": 0, "gelu": 1}   # gt_encoder_layer.act
+
+
+def _encoder_desc(x, lay, nhead, dropout_p, seed, training, ln_eps, act, params):
+    rows, d = x.shape
+    desc = EncoderLayerDesc()
+    desc.rows, desc.d_model, desc.ffn = rows, d, params[4].shape[0]
+    desc.nhead = nhead
+    desc.dtype = GT_BF16 if x.dtype == torch.bfloat16 else GT_F32
+    desc.compute = _compute_code()
+    desc.training = 1 if training else 0
+    desc.seq_desc = _ptr(lay.desc)
+    desc.num_seqs, desc.row_stride, desc.max_npos = lay.B, lay.row_stride, lay.max_npos
+    desc.work_items, desc.num_work = _ptr(getattr(lay, "work", None)), getattr(lay, "num_work", 0)
+    desc.dropout_p, desc.ln_eps, desc.seed = float(dropout_p), float(ln_eps), int(seed)
+    desc.act = ENC_ACT[act]
+    for name, p in zip(("in_w", "in_b", "out_w", "out_b", "l1_w", "l1_b", "l2_w", "l2_b", "n1_w", "n1_b", "n2_w", "n2_b"), params):
+        setattr(desc, name, _ptr(_f32c(p)))
+    return desc
+
+
 class _EncoderLayer(torch.autograd.Function):
+    """gt_encoder_layer_*: x (rows, d) -> y (rows, d).  pooled (gt_encoder_layer_pooled_*, the LAST encoder layer under cls / last
+    pooling): -> y (B, d), the layer's output in the pooled row of every sequence only (what transformer_out[-1] reads,
+    models/gnn_transformer.py:113-114)."""
+
     @staticmethod
-    def forward(ctx, x, lay, nhead, dropout_p, seed, training, ln_eps, act, *params):
+    def forward(ctx, x, lay, pooled, nhead, dropout_p, seed, training, ln_eps, act, *params):
         L = _bind()
         x = x.contiguous()
-        rows, d = x.shape
-        desc = EncoderLayerDesc()
-        desc.rows, desc.d_model, desc.ffn = rows, d, params[4].shape[0]
-        desc.nhead = nhead
-        desc.dtype = GT_BF16 if x.dtype == torch.bfloat16 else GT_F32
-        desc.compute = _compute_code()
-        desc.training = 1 if training else 0
-        desc.seq_desc = _ptr(lay.desc)
-        desc.num_seqs, desc.row_stride, desc.max_npos = lay.B, lay.row_stride, lay.max_npos
-        desc.work_items, desc.num_work = _ptr(getattr(lay, "work", None)), getattr(lay, "num_work", 0)
-        desc.dropout_p, desc.ln_eps, desc.seed = float(dropout_p), float(ln_eps), int(seed)
-        desc.act = ENC_ACT[act]
-        for name, p in zip(("in_w", "in_b", "out_w", "out_b", "l1_w", "l1_b", "l2_w", "l2_b", "n1_w", "n1_b", "n2_w",
-                            "n2_b"), params):
-            setattr(desc, name, _ptr(_f32c(p)))
-        saved = _bytes(L.gt_encoder_layer_saved_bytes(C.byref(desc)), x.device)
+        desc = _encoder_desc(x, lay, nhead, dropout_p, seed, training, ln_eps, act, params)
+        fn = "gt_encoder_layer_pooled" if pooled else "gt_encoder_layer"
+        saved = _bytes(getattr(L, fn + "_saved_bytes")(C.byref(desc)), x.device)
         if not getattr(lay, "exact", True):
             saved.zero_()   # device-built layout (upper-bound row count): the attention kernels skip the rows past the true count
-        y = torch.empty_like(x)
-        _lib.check(L.gt_encoder_layer_fwd(C.byref(desc), _ptr(x), _ptr(y), _ptr(saved), _stream()), "gt_encoder_layer_fwd")
+        if pooled:
+            y = torch.empty((lay.B, x.shape[1]), dtype=x.dtype, device=x.device)
+            rc = L.gt_encoder_layer_pooled_fwd(C.byref(desc), _ptr(x), _ptr(lay.last_rows), _ptr(y), _ptr(saved), _stream())
+        else:
+            y = torch.empty_like(x)
+            rc = L.gt_encoder_layer_fwd(C.byref(desc), _ptr(x), _ptr(y), _ptr(saved), _stream())
+        _lib.check(rc, fn + "_fwd")
         ctx.save_for_backward(x, saved, *params)
-        ctx.desc, ctx.lay = desc, lay
+        ctx.desc, ctx.lay, ctx.fn = desc, lay, fn
         return y
 
     @staticmethod
@@ -154,80 +171,23 @@ class _EncoderLayer(torch.autograd.Function):
         L = _bind()
         x, saved = ctx.saved_tensors[:2]
         params = ctx.saved_tensors[2:]
-        desc = ctx.desc
+        desc, fn = ctx.desc, ctx.fn
         dy = dy.contiguous()
         if dy.dtype != x.dtype:
             dy = dy.to(x.dtype)
         dx = torch.empty_like(x)
         grads = torch.empty(L.gt_encoder_layer_grad_elems(C.byref(desc)), dtype=torch.float32, device=x.device)
-        ws_bytes = L.gt_encoder_layer_workspace_bytes(C.byref(desc))
+        ws_bytes = getattr(L, fn + "_workspace_bytes")(C.byref(desc))
         ws = _bytes(ws_bytes, x.device)
         if not getattr(ctx.lay, "exact", True):
             ws.zero_()
-        _lib.check(L.gt_encoder_layer_bwd(C.byref(desc), _ptr(x), _ptr(dy), _ptr(saved), _ptr(dx), _ptr(grads), _ptr(ws),
-                                          ws_bytes, _stream()), "gt_encoder_layer_bwd")
-        return (dx, None, None, None, None, None, None, None, *_split(grads, params))
-
-
-class _EncoderLayerPooled(torch.autograd.Function):
-    """The LAST encoder layer under cls / last pooling (gt_encoder_layer_pooled_*): x (rows, d) -> y (B, d), the layer's output in the
-    pooled row of every sequence only (what transformer_out[-1] reads, models/gnn_transformer.py:113-114)."""
-
-    @staticmethod
-    def forward(ctx, x, lay, nhead, dropout_p, seed, training, ln_eps, act, *params):
-        L = _bind()
-        x = x.contiguous()
-        rows, d = x.shape
-        desc = EncoderLayerDesc()
-        desc.rows, desc.d_model, desc.ffn = rows, d, params[4].shape[0]
-        desc.nhead = nhead
-        desc.dtype = GT_BF16 if x.dtype == torch.bfloat16 else GT_F32
-        desc.compute = _compute_code()
-        desc.training = 1 if training else 0
-        desc.seq_desc = _ptr(lay.desc)
-        desc.num_seqs, desc.row_stride, desc.max_npos = lay.B, lay.row_stride, lay.max_npos
-        desc.work_items, desc.num_work = _ptr(getattr(lay, "work", None)), getattr(lay, "num_work", 0)
-        desc.dropout_p, desc.ln_eps, desc.seed = float(dropout_p), float(ln_eps), int(seed)
-        desc.act = ENC_ACT[act]
-        for name, p in zip(("in_w", "in_b", "out_w", "out_b", "l1_w", "l1_b", "l2_w", "l2_b", "n1_w", "n1_b", "n2_w",
-                            "n2_b"), params):
-            setattr(desc, name, _ptr(_f32c(p)))
-        zero = not getattr(lay, "exact", True)
-        saved = _bytes(L.gt_encoder_layer_pooled_saved_bytes(C.byref(desc)), x.device)
-        if zero:
-            saved.zero_()
-        y = torch.empty((lay.B, d), dtype=x.dtype, device=x.device)
-        _lib.check(L.gt_encoder_layer_pooled_fwd(C.byref(desc), _ptr(x), _ptr(lay.last_rows), _ptr(y), _ptr(saved), _stream()),
-                   "gt_encoder_layer_pooled_fwd")
-        ctx.save_for_backward(x, saved, *params)
-        ctx.desc, ctx.lay = desc, lay
-        return y
-
-    @staticmethod
-    def backward(ctx, dy):
-        L = _bind()
-        x, saved = ctx.saved_tensors[:2]
-        params = ctx.saved_tensors[2:]
-        desc = ctx.desc
-        dy = dy.contiguous()
-        if dy.dtype != x.dtype:
-            dy = dy.to(x.dtype)
-        dx = torch.empty_like(x)
-        grads = torch.empty(L.gt_encoder_layer_grad_elems(C.byref(desc)), dtype=torch.float32, device=x.device)
-        ws_bytes = L.gt_encoder_layer_pooled_workspace_bytes(C.byref(desc))
-        ws = _bytes(ws_bytes, x.device)
-        if not getattr(ctx.lay, "exact", True):
-            ws.zero_()
-        _lib.check(L.gt_encoder_layer_pooled_bwd(C.byref(desc), _ptr(x), _ptr(ctx.lay.last_rows), _ptr(dy), _ptr(saved), _ptr(dx), _ptr(grads),
-                                                 _ptr(ws), ws_bytes, _stream()), "gt_encoder_layer_pooled_bwd")
-        return (dx, None, None, None, None, None, None, None, *_split(grads, params))
-
-
-def encoder_layer_pooled(x, mod, lay, nhead, dropout_p, seed, training, activation="relu"):
-    return _EncoderLayerPooled.apply(x, lay, nhead, dropout_p, seed, training, mod.norm1.eps, activation, *encoder_layer_params(mod))
-
-
-ENC_ACT = {"relu": 0, "gelu": 1}   # gt_encoder_layer.act
+        tail = (_ptr(dy), _ptr(saved), _ptr(dx), _ptr(grads), _ptr(ws), ws_bytes, _stream())
+        if fn == "gt_encoder_layer_pooled":
+            rc = L.gt_encoder_layer_pooled_bwd(C.byref(desc), _ptr(x), _ptr(ctx.lay.last_rows), *tail)
+        else:
+            rc = L.gt_encoder_layer_bwd(C.byref(desc), _ptr(x), *tail)
+        _lib.check(rc, fn + "_bwd")
+        return (dx, None, None, None, None, None, None, None, None, *_split(grads, params))
 
 
 def encoder_layer_eligible(mod, x, activation):
@@ -236,7 +196,11 @@ def encoder_layer_eligible(mod, x, activation):
 
 
 def encoder_layer(x, mod, lay, nhead, dropout_p, seed, training, activation="relu"):
-    return _EncoderLayer.apply(x, lay, nhead, dropout_p, seed, training, mod.norm1.eps, activation, *encoder_layer_params(mod))
+    return _EncoderLayer.apply(x, lay, False, nhead, dropout_p, seed, training, mod.norm1.eps, activation, *encoder_layer_params(mod))
+
+
+def encoder_layer_pooled(x, mod, lay, nhead, dropout_p, seed, training, activation="relu"):
+    return _EncoderLayer.apply(x, lay, True, nhead, dropout_p, seed, training, mod.norm1.eps, activation, *encoder_layer_params(mod))
 
 
 # ------------------------------------------------------------------------------------------------
