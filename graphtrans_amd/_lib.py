@@ -14,6 +14,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("GT_LIB_PATH") or os.path.join(_HERE, "libgraphtrans_hip.so")   # GT_LIB_PATH: A/B builds
 
 GT_F32, GT_BF16 = 0, 1
+GT_COMPUTE_F32_HIGH = 2   # enum gt_compute: fp32 compute that allows three bf16 products per fp32 product ("high")
 GT_CONV_GCN, GT_CONV_GIN = 0, 1
 GT_EDGE_NONE, GT_EDGE_LINEAR, GT_EDGE_TABLES, GT_EDGE_DENSE = 0, 1, 2, 3
 
@@ -86,6 +87,7 @@ SIGNATURES = {
     "gt_defer_flush": (_i, [_p]),
     "gt_defer_end": (_i, []),
     "gt_linear_rows_ok": (_i, [_i, _i, _i, _p, _i64, _i64, _i64]),
+    "gt_linear_products": (_i, [_i, _i, _i, _i, _p, _i64, _i64, _i64]),
     "gt_linear_set_rows": (_i, [_p]),
     "gt_linear_rows_layernorm_ok": (_i, [_i64]),
     "gt_linear_set_rows_layernorm": (_i, [_p, _p, _p, _f, _p, _p, _p]),

@@ -43,6 +43,9 @@ static inline bool gt_dbg_empty() {
 
 #include "../../include/graphtrans_hip.h"
 
+// a `compute` argument as the dispatchers read it: GT_COMPUTE_F32_HIGH is fp32 compute (the permission rides in the call records)
+static inline int gt_compute_base(int compute) { return compute == GT_COMPUTE_F32_HIGH ? GT_F32 : compute; }
+
 #define GT_WAVE 64
 
 // thread-local last-error string (C-ABI contract: never throws, never exits)

@@ -828,12 +828,12 @@ bool small_eligible(int x_dtype, int y_dtype, int64_t M, int64_t N, int64_t K, i
 // ---- exact-fp32 wide-tile path (linear32.h): the big-M GEMMs of the message-passing side --------------------------------
 constexpr int64_t W32_MIN_M = 1024;   // below this the grid of 64-row blocks cannot fill the chip: 128-wide tiles + splits
 
-bool w32_eligible(int compute, int x_dtype, int64_t M, int groups) {
-  return compute == GT_F32 && x_dtype == GT_F32 && groups == 1 && M >= W32_MIN_M;
+bool w32_eligible(int compute, int x_dtype, int64_t M, int groups) {   // (compute: a gt_compute value, "high" is fp32)
+  return gt_compute_base(compute) == GT_F32 && x_dtype == GT_F32 && groups == 1 && M >= W32_MIN_M;
 }
 // grouped launches of the bf16x6 kernel (k_lin3, blockIdx.y = group): fp32 rows in and out, 16-byte chunks of every row
 bool g3_eligible(int compute, int x_dtype, int y_dtype, int64_t M, int64_t N, int64_t K, int64_t ldx, int64_t ldy) {
-  return compute == GT_F32 && x_dtype == GT_F32 && y_dtype == GT_F32 && M >= W32_MIN_M && N % 4 == 0 && K % 4 == 0 && ldx % 4 == 0 &&
+  return gt_compute_base(compute) == GT_F32 && x_dtype == GT_F32 && y_dtype == GT_F32 && M >= W32_MIN_M && N % 4 == 0 && K % 4 == 0 && ldx % 4 == 0 &&
          ldy % 4 == 0;
 }
 
@@ -970,6 +970,7 @@ bool fwd_grouped3(const LinFwd& f, const LinArgs& a, int&) {
   w.a = f.x; w.bias = f.bias; w.out = f.y; w.M = f.M; w.Nout = f.N; w.Kc = f.K; w.lda = f.ldx; w.ldw = f.K; w.ldo = f.ldy;
   w.act = f.act; w.inv_keep = a.inv_keep; w.thr = a.thr; w.s0 = a.s0; w.s1 = a.s1;
   w.w3 = img; w.groups = f.groups; w.g_a = f.x_group_stride; w.g_o = f.y_group_stride; w.g_img = spacing; w.g_b = (int)f.N;
+  w.high = f.high;
   GtProfScope pk__(GT_PROF_GEMM_KERNEL, "k_lin3[fwd]", stream, LIN_DIMS(f));
   w3_launch<false>(f.x_dtype, f.y_dtype, stream, w);
   return true;
@@ -982,6 +983,7 @@ bool fwd_wide(const LinFwd& f, const LinArgs& a, int& rc) {
   L32Args w{};
   w.a = f.x; w.w = f.weight; w.bias = f.bias; w.out = f.y; w.M = f.M; w.Nout = f.N; w.Kc = f.K; w.lda = f.ldx; w.ldw = f.K; w.ldo = f.ldy;
   w.act = f.act; w.gout = f.gout; w.inv_keep = a.inv_keep; w.thr = a.thr; w.s0 = a.s0; w.s1 = a.s1;
+  w.high = f.high;
   // a prepared bf16x3 image of this weight (gt_w3_bind): the fp32-accurate GEMM on the bf16 matrix pipe (linear3x.h);
   // bf16 rows need K % 8 (their 16-byte chunks are whole k-groups)
   w.w3 = (f.x_dtype == GT_F32 || f.K % 8 == 0) ? w3_lookup(f.weight, f.N, f.K, false) : nullptr;
@@ -1033,8 +1035,11 @@ void fwd_tiled(const LinFwd& f, LinArgs a) {
 }
 }  // namespace
 
-int lin_fwd(const LinFwd& f) {
+int lin_fwd(const LinFwd& f_) {
   const char* fn = "linear_fwd_impl";
+  LinFwd f = f_;   // (the one place a forward's `compute` is normalised: linear_call.h)
+  f.high = f.compute == GT_COMPUTE_F32_HIGH;
+  f.compute = gt_compute_base(f.compute);
   LIN_CHECK_ARG(fn, !f.map.rows || (f.groups == 1 && rows_eligible(f.compute, f.x_dtype, f.y_dtype, f.weight, f.M, f.N, f.K)),
                 "gt_linear_set_rows: this GEMM does not take a row map (ask gt_linear_rows_ok)");
   int rc = check_call(fn, "gt_linear_fwd", f.x_dtype, f.y_dtype, f.compute, f.M, f.N, f.K, f.ldx, f.ldy, f.x2 ? f.x_split : f.K, f.groups,
@@ -1091,6 +1096,7 @@ extern "C" int gt_linear_fwd_gelu(int x_dtype, int y_dtype, int compute, const v
 }
 
 extern "C" size_t gt_linear_bwd_workspace_bytes(int compute, int64_t M, int64_t N, int64_t K) {
+  compute = gt_compute_base(compute);   // "high" sizes as fp32
   if (compute == GT_F32 && M >= W32_MIN_M) {   // wide-tile fp32 path: [dW / db partials | W^T for the dX GEMM]
     const int nt = w32_pick_nt(N);
     const int splits = w32_dw_splits(M, (int)gt_cdiv(K, 64), (int)gt_cdiv(gt_cdiv(N, 16), nt), false);   // the larger of the two configurations
@@ -1204,6 +1210,44 @@ void small_dw(const LinBwd& c, const BwdState& s) {   // the one-wave-per-tile d
   }
   dw_book(c, stream);
 }
+// "High" only: the weight gradient of a SHORT-M call on a bound weight.  k_small_dw has no three-product form (it multiplies in fp32), the
+// pipelined split kernel has, and it takes any M (its M range is cut into 32-row stages): from one whole stage on (M >= 32) the dW of a
+// call that would otherwise run k_small_dw runs k_lin3r_dw<.., HI> -- one split per 256 rows, within what the caller's workspace (sized as
+// for compute = 0) holds.  Below 32 rows, without a bound image or a workspace, and under compute = 0 / 1, nothing changes: k_small_dw.
+bool high_small_dw_ok(int x_dtype, int y_dtype, const float* weight, int64_t M, int64_t N, int64_t K, int64_t ldx, int64_t ldy, int groups) {
+  if (M < 32 || !small_eligible(x_dtype, y_dtype, M, N, K, ldx, ldy, groups) || !w3_lookup(weight, N, K, false)) return false;
+  L32DwArgs d{};
+  d.N = N; d.K = K; d.ldy = ldy; d.ldx = ldx;
+  return w3r_dw_ok(y_dtype, x_dtype, d);
+}
+int bwd_high_small_dw(const LinBwd& c, BwdState& s) {
+  const int64_t M = c.M, N = c.N, K = c.K;
+  if (!c.high || !s.dw || c.x2 || c.map.rows || !c.workspace || c.workspace_bytes < s.need ||
+      !high_small_dw_ok(c.x_dtype, c.y_dtype, c.weight, M, N, K, c.ldx, c.ldy, c.groups))
+    return GT_OK;
+  L32DwArgs d{};
+  d.dy = c.dy; d.ymask = s.ymask; d.x = c.x; d.inv_keep = s.inv_keep;
+  d.M = M; d.N = N; d.K = K; d.ldy = c.ldy; d.ldx = c.ldx; d.high = 1;
+  if (!w3r_dw_ok(c.y_dtype, c.x_dtype, d)) return GT_OK;   // (the operands' alignment)
+  hipStream_t stream = dw_fork(c, true);
+  d.nkb = (int)gt_cdiv(K, W3D_T); d.nnb = (int)gt_cdiv(N, W3D_T);
+  int splits = w3_dw_splits(M, d.nkb * d.nnb);
+  const int cap = dw_splits(M, N, K, GT_F32);   // the workspace holds this many partial copies (gt_linear_bwd_workspace_bytes)
+  if (splits > cap) splits = cap;
+  d.m_per_split = gt_cdiv(gt_cdiv(M, splits), 32) * 32;
+  d.part = reinterpret_cast<float*>(c.workspace);
+  d.dbpart = c.dbias ? d.part + (size_t)splits * N * K : nullptr;
+  d.splits = splits;
+  dim3 grid((unsigned)(gt_cdiv(splits, 8) * 8 * d.nkb * d.nnb));
+  {
+    GtProfScope pk__(GT_PROF_GEMM_KERNEL, "k_lin3r_dw", stream, LIN_DIMS(c));
+    w3r_launch_dw(grid, stream, d);
+  }
+  dw_reduce(stream, false, d.part, splits, N * K, c.dweight, d.dbpart, c.dbias ? N : 0, c.dbias);
+  dw_book(c, stream);
+  s.dw = false;
+  return GT_OK;
+}
 int bwd_small(const LinBwd& c, BwdState& s) {   // short M (linear_small.h): no LDS, no partials
   if (!small_eligible(c.x_dtype, c.y_dtype, c.M, c.N, c.K, c.ldx, c.ldy, c.groups)) return GT_OK;
   if (s.dx) {
@@ -1231,6 +1275,7 @@ int bwd_grouped3_dx(const LinBwd& c, BwdState& s) {
   w.a = c.dy; w.amask = s.ymask; w.out = c.dx; w.add1 = c.dx_add1; w.add2 = c.dx_add2;
   w.M = c.M; w.Nout = c.K; w.Kc = c.N; w.lda = c.ldy; w.ldw = c.N; w.ldo = c.ldx; w.inv_keep = s.inv_keep;
   w.w3 = img; w.groups = c.groups; w.g_a = c.y_group_stride; w.g_o = c.x_group_stride; w.g_img = spacing;
+  w.high = c.high;
   GtProfScope pk__(GT_PROF_GEMM_KERNEL, "k_lin3[dx]", stream, LIN_DIMS(c));
   w3_launch<true>(c.y_dtype, c.x_dtype, stream, w);
   s.dx = false;
@@ -1247,6 +1292,7 @@ int bwd_grouped3_dw(const LinBwd& c, BwdState& s) {
   d.dy = c.dy; d.ymask = s.ymask; d.x = c.x; d.inv_keep = s.inv_keep;
   d.M = M; d.N = N; d.K = K; d.ldy = c.ldy; d.ldx = c.ldx;
   d.groups = c.groups; d.g_y = c.y_group_stride; d.g_x = c.x_group_stride;
+  d.high = c.high;
   if (!w3_lookup_grouped(c.weight, N, K, c.groups, false, &spacing) || !w3r_dw_ok(c.y_dtype, c.x_dtype, d)) return GT_OK;
   // (the weight gradient alone goes to the overlap stream: a dX that the generic kernels below still owe stays on the caller's)
   hipStream_t stream = dw_fork(c, true);
@@ -1295,6 +1341,7 @@ int wide_dx(const LinBwd& c, const BwdState& s, float* wt) {
   L32Args w{};
   w.a = c.dy; w.amask = s.ymask; w.w = wt; w.out = c.dx; w.add1 = c.dx_add1; w.add2 = c.dx_add2;
   w.M = M; w.Nout = K; w.Kc = N; w.lda = c.ldy; w.ldw = N; w.ldo = c.ldx; w.inv_keep = s.inv_keep;
+  w.high = c.high;
   if (c.bn_part && c.x_dtype == GT_F32 && c.y_dtype == GT_F32) {
     w.bn_x = c.bn_x; w.bn_ldx = c.bn_ldx; w.bn_mean = c.bn_mean; w.bn_rstd = c.bn_rstd; w.bn_w = c.bn_w; w.bn_b = c.bn_b;
     w.bn_relu = c.bn_relu; w.bn_part = c.bn_part;
@@ -1326,6 +1373,7 @@ int wide_dw(const LinBwd& c, const BwdState& s, hipStream_t stream, float* part,
   d.dy = c.dy; d.ymask = s.ymask; d.x = c.x; d.inv_keep = s.inv_keep;
   d.M = M; d.N = N; d.K = K; d.ldy = c.ldy; d.ldx = c.ldx;
   if (c.x2) { d.x2 = c.x2; d.x_split = c.x_split; d.ldx2 = c.ldx2; }
+  d.high = c.high;
   // weights with bound images run the bf16x6 dW kernel too (160 x 160 output tiles, split over M; linear3x.h)
   const bool split3 = c.x_dtype == GT_F32 && w3_lookup(c.weight, N, K, false) != nullptr && (c.y_dtype == GT_F32 || N % 8 == 0);
   if (c.map.rows && !split3) { gt_set_error("gt_linear_set_rows: needs the bound weight image"); return GT_ERR_UNSUPPORTED; }
@@ -1512,8 +1560,11 @@ int bwd_split_dw(const LinBwd& c, BwdState& s) {
 }
 }  // namespace
 
-int lin_bwd(const LinBwd& c) {
+int lin_bwd(const LinBwd& c_) {
   const char* fn = "gt_linear_bwd_grouped";
+  LinBwd c = c_;   // (the one place a backward's `compute` is normalised: linear_call.h)
+  c.high = c.compute == GT_COMPUTE_F32_HIGH;
+  c.compute = gt_compute_base(c.compute);
   if (c.bcast && c.dx && !gt_linear_bwd_bcast_ok(c.compute, c.x_dtype, c.y_dtype, c.weight, c.M, c.N, c.K)) {
     gt_set_error("gt_linear_bwd_bcast: this call does not run on the register-row kernel (ask gt_linear_bwd_bcast_ok)");
     return GT_ERR_UNSUPPORTED;
@@ -1541,7 +1592,7 @@ int lin_bwd(const LinBwd& c) {
   s.need = (size_t)c.groups * need1;
   s.g_part = (int64_t)(need1 / sizeof(float));
   static int (*const families[])(const LinBwd&, BwdState&) = {
-      bwd_small, bwd_grouped3_dx, bwd_grouped3_dw, bwd_wide, bwd_bf16_image_dx, bwd_gate_out_spent, bwd_heads_dx, bwd_tiled_dx, bwd_small_wide_dw,
+      bwd_high_small_dw, bwd_small, bwd_grouped3_dx, bwd_grouped3_dw, bwd_wide, bwd_bf16_image_dx, bwd_gate_out_spent, bwd_heads_dx, bwd_tiled_dx, bwd_small_wide_dw,
       bwd_split_dw};
   for (auto family : families) {
     if ((rc = family(c, s)) != GT_OK) return rc;
@@ -1639,6 +1690,34 @@ extern "C" int gt_linear_cat2_ok(int compute, const float* weight, int64_t M, in
 }
 // ---- a row map on the output (forward) / on dY (backward): gnn2transformer writing and reading the Transformer's token rows in place
 // (models/gnn_transformer.py:92-96, modules/utils.py:5-29: no pad / unpad pass over the node rows) -----------------------------------
+// bf16 products per fp32 product of a plain call under the current bindings (include/graphtrans_hip.h): the dispatchers' own tests
+extern "C" int gt_linear_products(int which, int x_dtype, int y_dtype, int compute, const float* weight, int64_t M, int64_t N, int64_t K) {
+  const bool high = compute == GT_COMPUTE_F32_HIGH;
+  if (which < 0 || which > 2 || !weight || N <= 0 || K <= 0) return 0;
+  if (which == 2 && high && gt_compute_base(compute) == GT_F32 && high_small_dw_ok(x_dtype, y_dtype, weight, M, N, K, K, N, 1)) return 3;   // bwd_high_small_dw
+  if (!w32_eligible(compute, x_dtype, M, 1)) return 0;
+  if (which == 0) {   // fwd_heads comes first, then fwd_wide
+    if (heads_shape_ok(x_dtype, y_dtype, M, N, K, K, N, 1)) return 0;
+    L32Args w{};
+    w.w3 = (x_dtype == GT_F32 || K % 8 == 0) ? w3_lookup(weight, N, K, false) : nullptr;
+    if (!w.w3) return 0;
+    w.M = M; w.Nout = N; w.Kc = K; w.lda = K; w.ldo = N; w.high = high;
+    return (w3r_ok(x_dtype, y_dtype, w) ? high : w3_high(x_dtype, y_dtype, w)) ? 3 : 6;
+  }
+  if (which == 1) {   // wide_dx
+    L32Args w{};
+    w.w3 = (y_dtype != GT_F32 && N % 8) ? nullptr : w3_lookup(weight, N, K, true);
+    if (!w.w3) return 0;
+    w.M = M; w.Nout = K; w.Kc = N; w.lda = N; w.ldo = K; w.high = high;
+    return (w3r_ok(y_dtype, x_dtype, w) ? high : w3_high(y_dtype, x_dtype, w)) ? 3 : 6;
+  }
+  // wide_dw
+  if (!(x_dtype == GT_F32 && w3_lookup(weight, N, K, false) != nullptr && (y_dtype == GT_F32 || N % 8 == 0))) return 0;
+  L32DwArgs d{};
+  d.M = M; d.N = N; d.K = K; d.ldy = N; d.ldx = K; d.high = high;
+  return (w3r_dw_ok(y_dtype, x_dtype, d) && w3r_dw_high(d)) ? 3 : 6;
+}
+
 extern "C" int gt_linear_rows_ok(int compute, int x_dtype, int y_dtype, const float* weight, int64_t M, int64_t N, int64_t K) {
   return (rows_eligible(compute, x_dtype, y_dtype, weight, M, N, K)) ? 1 : 0;
 }

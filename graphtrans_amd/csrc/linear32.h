@@ -68,6 +68,9 @@ struct L32Args {
   void* ln_out;              // [.][ldo], TO
   float *ln_mean, *ln_rstd;
   float ln_eps;
+  // host side only (the launchers of linear3x.h / linear3r.h): the call allows "high", three bf16 products per fp32 product
+  // (sits in the struct's tail padding: the kernels' argument layout is what it was)
+  int high;
 };
 
 // 16-byte chunk of TA -> up to 8 floats
@@ -373,6 +376,8 @@ struct L32DwArgs {
   // k_lin3r_dw only -- a GROUPED launch (blockIdx.y = group): group g reads dy / ymask + g * g_y and x + g * g_x elements and writes
   // its partials g * g_part floats behind part / dbpart
   int groups;               // 0 / 1 = one GEMM
+  int high;                 // host side only (w3r_launch_dw): the call allows "high", three bf16 products per fp32 product
+                            // (sits in the padding in front of g_y: the kernels' argument layout is what it was)
   int64_t g_y, g_x, g_part;
 };
 

@@ -24,6 +24,8 @@
 // Covered: fp32 rows in and out, no gate / dropout / GELU / row maps / LayerNorm epilogue / virtual concatenation (those keep k_lin3),
 // 8 < n-tiles per column block <= 20, M >= W3R_MIN_M (the grid is ceil(M / 128) x column blocks: below ~16 k rows k_lin3's 64-row
 // blocks fill the chip better).
+// "High" (linear3x.h): k_lin3r<NTW, CH, true> keeps two planes of each operand -- two row planes, 2 x NTB KB per LDS stage (80 KB for both
+// stages at NTW = 10), 12 MFMAs per tile pair and k-step, the same epilogue.
 #pragma once
 
 #ifndef W3R_ABL
@@ -32,11 +34,14 @@
 
 constexpr int64_t W3R_MIN_M = 12288;
 
-template <int NTW, int CH>
+// HI ("high", linear3x.h): two planes of each operand and the three products of order <= 2^-8 -- plane 2 of the image is not fetched,
+// the rows are split two ways, a stage holds 2 x NTB KB.
+template <int NTW, int CH, bool HI = false>
 __global__ void __launch_bounds__(256 * CH, CH) k_lin3r(L32Args a) {
   constexpr int NTB = CH * NTW;               // n-tiles per LDS stage and plane
   constexpr int NWV = 4 * CH;                 // waves: 4 row groups x CH column parts
-  constexpr int WSTAGE = 3 * NTB * 1024;
+  constexpr int NPL = HI ? 2 : 3;             // planes kept of each operand
+  constexpr int WSTAGE = NPL * NTB * 1024;
   extern __shared__ __attribute__((aligned(1024))) unsigned char smem3r[];
   const int tid = threadIdx.x, lane = tid & 63;
   const int wid = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -77,25 +82,26 @@ __global__ void __launch_bounds__(256 * CH, CH) k_lin3r(L32Args a) {
     }
   };
   // planes of the current k-step (fa) and of the next one (fn) as 32-bit words: word e of plane p of row tile i = k-pair e of the chunk
-  uint32_t fa[2][3][4], fn[2][3][4];
-  auto split_pair = [&](uint32_t (&dst)[2][3][4], int i, int e) {   // k-pair e (0..3) of row tile i
+  uint32_t fa[2][NPL][4], fn[2][NPL][4];
+  auto split_pair = [&](uint32_t (&dst)[2][NPL][4], int i, int e) {   // k-pair e (0..3) of row tile i
     const float4 u = e < 2 ? raw[i][0] : raw[i][1];
     const bool z = e < 2 ? z0 : z1;
     const float lo = z ? 0.f : ((e & 1) ? u.z : u.x), hi = z ? 0.f : ((e & 1) ? u.w : u.y);
-    w3_split_pair(lo, hi, dst[i][0][e], dst[i][1][e], dst[i][2][e]);
+    if constexpr (HI) w3_split_pair2(lo, hi, dst[i][0][e], dst[i][1][e]);
+    else w3_split_pair(lo, hi, dst[i][0][e], dst[i][1][e], dst[i][NPL - 1][e]);
   };
-  auto frag = [&](const uint32_t (&src)[2][3][4], int i, int p) {
+  auto frag = [&](const uint32_t (&src)[2][NPL][4], int i, int p) {
     return __builtin_bit_cast(bf16x8_t, make_uint4(src[i][p][0], src[i][p][1], src[i][p][2], src[i][p][3]));
   };
   // ---- weight planes: piece i = plane i / NTB, tile i % NTB -> LDS offset i KB of the stage; wave w takes pieces w, w + 8, ...
   // Branch-free (the pieces are issued BETWEEN the MFMAs of a k-step, one basic block): a piece index past the stage's last one
   // repeats the last piece (same bytes to the same place), a tile past the image's last one repeats the last tile (never stored from).
-  constexpr int NPIECE = (3 * NTB + NWV - 1) / NWV;   // per wave and k-step
+  constexpr int NPIECE = (NPL * NTB + NWV - 1) / NWV;   // per wave and k-step
   auto dma_piece = [&](int ks, int buf, int q) {
     const unsigned char* src = img + (int64_t)ks * 3 * plane_stride;
     unsigned char* dstb = smem3r + buf * WSTAGE;
     int i = q * NWV + wid;
-    i = i < 3 * NTB ? i : 3 * NTB - 1;
+    i = i < NPL * NTB ? i : NPL * NTB - 1;
     const int p = i / NTB, j = i % NTB;
     const int js = j < ntl ? j : ntl - 1;
     __builtin_amdgcn_global_load_lds((w3_glb_void*)(src + p * plane_stride + (int64_t)js * 1024), (w3_lds_void*)(dstb + i * 1024), 16, 0, 0);
@@ -127,12 +133,49 @@ __global__ void __launch_bounds__(256 * CH, CH) k_lin3r(L32Args a) {
     // front of the second row tile's split, behind the first DMA piece)
     if constexpr (MORE) __builtin_amdgcn_s_waitcnt(0x0F70);   // vmcnt(0)
     const unsigned char* sW = smem3r + (ks & 1) * WSTAGE + (ch * NTW) * 1024 + n * 64 + swz;
-    bf16x8_t fw[2][2][3];
+    bf16x8_t fw[2][2][NPL];
 #pragma unroll
     for (int jj = 0; jj < 2; ++jj)
 #pragma unroll
-      for (int p = 0; p < 3; ++p) fw[0][jj][p] = *reinterpret_cast<const bf16x8_t*>(sW + (p * NTB + jj) * 1024);
+      for (int p = 0; p < NPL; ++p) fw[0][jj][p] = *reinterpret_cast<const bf16x8_t*>(sW + (p * NTB + jj) * 1024);
     __builtin_amdgcn_sched_barrier(0);
+    if constexpr (HI) {
+      // "high": NP tile pairs x 12 MFMAs in three groups, (w1, a0), (w0, a1), (w0, a0).  The same side work in half the room:
+      //   * the four fragment reads of pair p + 1 in front of groups 0, 1, 2, 2;
+      //   * MORE: the 8 k-pairs of the next rows' two-way split (~8 VALU each) in twos in front of groups 0 and 2 of pairs 0 and 1,
+      //     the row loads of k-step + 2 in front of group 0 of pair 2, and ONE DMA piece of the next stage in front of group 1 of
+      //     every pair (NPIECE <= NP: a piece is always followed by a group of MFMAs, never by another piece).
+      static_assert(!HI || (NPIECE <= NP && NP >= 3), "one DMA piece per tile pair; the row loads ride on pair 2");
+      constexpr int PW[3] = {1, 0, 0}, PA[3] = {0, 1, 0};   // entries 3, 4, 5 of the six-product tables
+#pragma unroll
+      for (int pr = 0; pr < NP; ++pr) {
+        const int cur = pr & 1, jp = 2 * pr;
+#pragma unroll
+        for (int t = 0; t < 3; ++t) {
+          if (pr + 1 < NP) {
+#pragma unroll
+            for (int r = (t == 2 ? 2 : t); r <= (t == 2 ? 3 : t); ++r)
+              fw[cur ^ 1][r >> 1][r & 1] = *reinterpret_cast<const bf16x8_t*>(sW + ((r & 1) * NTB + jp + 2 + (r >> 1)) * 1024);
+          }
+          if constexpr (MORE) {
+            if (pr < 2 && t != 1) {
+              const int e8 = pr * 4 + (t == 0 ? 0 : 2);   // 0, 2, 4, 6
+              split_pair(fn, e8 >> 2, e8 & 3);
+              split_pair(fn, e8 >> 2, (e8 & 3) + 1);
+            }
+            if (pr == 2 && t == 0) load_rows(ks + 2 < nks ? ks + 2 : nks - 1);
+            if (t == 1 && pr < NPIECE) dma_piece(ks + 1, (ks + 1) & 1, pr);
+          }
+          __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+          for (int jj = 0; jj < 2; ++jj)
+#pragma unroll
+            for (int i = 0; i < 2; ++i)
+              acc[i][jp + jj] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fw[cur][jj][PW[t]], frag(fa, i, PA[t]), acc[i][jp + jj], 0, 0, 0);
+          __builtin_amdgcn_sched_barrier(0);
+        }
+      }
+    } else {
 #pragma unroll
     for (int pr = 0; pr < NP; ++pr) {
       const int cur = pr & 1, jp = 2 * pr;
@@ -168,11 +211,12 @@ __global__ void __launch_bounds__(256 * CH, CH) k_lin3r(L32Args a) {
         __builtin_amdgcn_sched_barrier(0);
       }
     }
+    }
     if constexpr (MORE) {
 #pragma unroll
       for (int i = 0; i < 2; ++i)
 #pragma unroll
-        for (int p = 0; p < 3; ++p)
+        for (int p = 0; p < NPL; ++p)
 #pragma unroll
           for (int e = 0; e < 4; ++e) fa[i][p][e] = (W3R_ABL & 16) ? (fa[i][p][e] ^ __float_as_uint(raw[i][e & 1].x)) : fn[i][p][e];
       __syncthreads();   // every wave has read stage ks & 1 and sees all of stage (ks + 1) & 1 (each wave waited for its own pieces)
@@ -311,9 +355,9 @@ __global__ void __launch_bounds__(256 * CH, CH) k_lin3r(L32Args a) {
   }
 }
 
-template <int NTW, int CH>
+template <int NTW, int CH, bool HI = false>
 void w3r_launch_one(dim3 grid, hipStream_t stream, const L32Args& a) {
-  constexpr int LDS = 2 * 3 * CH * NTW * 1024;
+  constexpr int LDS = 2 * (HI ? 2 : 3) * CH * NTW * 1024;
   static std::mutex mu;   // per instantiation: the > 64 KB dynamic-LDS opt-in is set once per device
   static bool done[16] = {false};
   int dev = 0;
@@ -321,11 +365,11 @@ void w3r_launch_one(dim3 grid, hipStream_t stream, const L32Args& a) {
   {
     std::lock_guard<std::mutex> lk(mu);
     if (dev < 0 || dev >= 16 || !done[dev]) {
-      (void)hipFuncSetAttribute((const void*)(k_lin3r<NTW, CH>), hipFuncAttributeMaxDynamicSharedMemorySize, LDS);
+      (void)hipFuncSetAttribute((const void*)(k_lin3r<NTW, CH, HI>), hipFuncAttributeMaxDynamicSharedMemorySize, LDS);
       if (dev >= 0 && dev < 16) done[dev] = true;
     }
   }
-  hipLaunchKernelGGL((k_lin3r<NTW, CH>), grid, dim3(256 * CH), LDS, stream, a);
+  hipLaunchKernelGGL((k_lin3r<NTW, CH, HI>), grid, dim3(256 * CH), LDS, stream, a);
 }
 
 // column blocks of the register-row kernel: as few as hold <= 20 tiles each; 0 = the shape is not covered
@@ -356,7 +400,10 @@ static inline void w3r_launch(hipStream_t stream, L32Args& a) {
   if (a.ntb > 16) w3r_launch_one<20, 1>(grid, stream, a);
   else w3r_launch_one<16, 1>(grid, stream, a);
 #else
-  if (a.ntb > 16) w3r_launch_one<10, 2>(grid, stream, a);
+  if (a.high) {   // three products (the call record's "high"): the two-plane instantiations
+    if (a.ntb > 16) w3r_launch_one<10, 2, true>(grid, stream, a);
+    else w3r_launch_one<8, 2, true>(grid, stream, a);
+  } else if (a.ntb > 16) w3r_launch_one<10, 2>(grid, stream, a);
   else w3r_launch_one<8, 2>(grid, stream, a);
 #endif
 }
@@ -391,13 +438,16 @@ static inline void w3r_launch(hipStream_t stream, L32Args& a) {
 // 73.1-73.6 k: the weight gradients run beside the critical path, their duration does not enter the step).  The 4-wave form ships;
 // GT_LIN3R_DW_PC=1 selects this one.
 // TN x TK: accumulator tiles per wave -> block = 32 TN x 32 TK outputs (5 x 5: 160 x 160; 7 x 4: 224 x 128 for the PNA towers' 204 x 340)
-template <bool MASK, bool ROWS, bool PC, int TN = 5, int TK = 5>
+// HI ("high", linear3x.h): two planes of dZ and of X per stage, the three products (z1, x0), (z0, x1), (z0, x0); a stage buffer shrinks
+// by a third, the next n-tile's two fragment reads ride in front of groups 0 and 1, the split chunks in front of groups 1 and 2.
+template <bool MASK, bool ROWS, bool PC, int TN = 5, int TK = 5, bool HI = false>
 __global__ void __launch_bounds__(PC ? 512 : 256, PC ? 2 : 1) k_lin3r_dw(L32DwArgs a) {
   static_assert(TK <= TN && TN <= 7, "one X chunk per n-tile of the MFMA loop at most");
   constexpr int ZT = 32 * TN, XT = 32 * TK;                // the block's extents along N and K
   constexpr int LDZ = ZT + 8, LDX = XT + 8, PLZ = 32 * LDZ, PLX = 32 * LDX;   // plane pitches / sizes (bf16 elements)
   constexpr int NCZ = TN, NCX = TK;                        // 16-byte chunks of the [32][ZT] / [32][XT] fp32 tiles per thread: chunk c = tid + 256 i
-  constexpr int STAGE_EL = 3 * PLZ + 3 * PLX;              // bf16 elements of one stage buffer: sZ[3] then sX[3]
+  constexpr int NPL = HI ? 2 : 3;                          // planes kept of each operand
+  constexpr int STAGE_EL = NPL * PLZ + NPL * PLX;          // bf16 elements of one stage buffer: sZ[NPL] then sX[NPL]
   extern __shared__ __attribute__((aligned(16))) unsigned char smem3rd[];
   gt_bf16* sbuf = reinterpret_cast<gt_bf16*>(smem3rd);
   const int lane = threadIdx.x & 63;
@@ -497,7 +547,7 @@ __global__ void __launch_bounds__(PC ? 512 : 256, PC ? 2 : 1) k_lin3r_dw(L32DwAr
   for (int i = 0; i < NCZ; ++i) dbs[i] = make_float4(0.f, 0.f, 0.f, 0.f);
   // split one chunk of a raw stage into the planes of buffer `buf`: which = 0 dZ chunk i (gated, summed into db), 1 X chunk i
   auto split_chunk = [&](const Raw& R, int64_t m0, int buf, int which, int i) {
-    gt_bf16* planes = sbuf + buf * STAGE_EL + which * 3 * PLZ;
+    gt_bf16* planes = sbuf + buf * STAGE_EL + which * NPL * PLZ;
     const int cr_ = which ? crx[i] : crz[i], cq_ = which ? cqx[i] : cqz[i];
     const int pl_ = which ? PLX : PLZ;
     const bool ok = m0 + cr_ < me && (which ? xcol[i] : (zcol[i] && !((R.none >> i) & 1u)));
@@ -511,6 +561,14 @@ __global__ void __launch_bounds__(PC ? 512 : 256, PC ? 2 : 1) k_lin3r_dw(L32DwAr
     if (!ok) v = make_float4(0.f, 0.f, 0.f, 0.f);
     if (!which) dbs[i] = gt_add4(dbs[i], v);
     if constexpr (W3RD_ABL & 4) return;
+    if constexpr (HI) {
+      uint32_t p1[2], p2[2];
+      w3_split_pair2(v.x, v.y, p1[0], p2[0]);
+      w3_split_pair2(v.z, v.w, p1[1], p2[1]);
+      gt_bf16* dst = planes + cr_ * (which ? LDX : LDZ) + cq_;
+      *reinterpret_cast<uint2*>(dst) = make_uint2(p1[0], p1[1]);
+      *reinterpret_cast<uint2*>(dst + pl_) = make_uint2(p2[0], p2[1]);
+    } else {
     uint32_t p1[2], p2[2], p3[2];
     w3_split_pair(v.x, v.y, p1[0], p2[0], p3[0]);
     w3_split_pair(v.z, v.w, p1[1], p2[1], p3[1]);
@@ -518,6 +576,7 @@ __global__ void __launch_bounds__(PC ? 512 : 256, PC ? 2 : 1) k_lin3r_dw(L32DwAr
     *reinterpret_cast<uint2*>(dst) = make_uint2(p1[0], p1[1]);
     *reinterpret_cast<uint2*>(dst + pl_) = make_uint2(p2[0], p2[1]);
     *reinterpret_cast<uint2*>(dst + 2 * pl_) = make_uint2(p3[0], p3[1]);
+    }
   };
 
   const int64_t nst = mb < me ? (me - mb + 31) / 32 : 0;
@@ -589,23 +648,38 @@ __global__ void __launch_bounds__(PC ? 512 : 256, PC ? 2 : 1) k_lin3r_dw(L32DwAr
     if constexpr (!PC) load_stage(RB, m2 < me ? m2 : (me > 32 ? me - 32 : mb));
     __builtin_amdgcn_sched_barrier(0);
     const gt_bf16* sZ = sbuf + buf * STAGE_EL;
-    const gt_bf16* sX = sZ + 3 * PLZ;
+    const gt_bf16* sX = sZ + NPL * PLZ;
     auto fload = [&](const gt_bf16* pl, int ld, int col0) {
       if constexpr (W3RD_ABL & 2) { Frag<gt_bf16> f; f.v = make_uint4((uint32_t)col0, (uint32_t)s, 3u, (uint32_t)lane); return f; }
       else return frag_load_tr(pl, ld, 0, col0, n, g);
     };
-    Frag<gt_bf16> fx[TK][3];
+    Frag<gt_bf16> fx[TK][NPL];
 #pragma unroll
     for (int i = 0; i < TK; ++i)
 #pragma unroll
-      for (int p = 0; p < 3; ++p) fx[i][p] = fload(sX + p * PLX, LDX, wk * 16 * TK + i * 16);
-    Frag<gt_bf16> fz[2][3];
+      for (int p = 0; p < NPL; ++p) fx[i][p] = fload(sX + p * PLX, LDX, wk * 16 * TK + i * 16);
+    Frag<gt_bf16> fz[2][NPL];
 #pragma unroll
-    for (int p = 0; p < 3; ++p) fz[0][p] = fload(sZ + p * PLZ, LDZ, wn * 16 * TN);
+    for (int p = 0; p < NPL; ++p) fz[0][p] = fload(sZ + p * PLZ, LDZ, wn * 16 * TN);
     __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
     for (int j = 0; j < TN; ++j) {
       const int cur = j & 1;
+      if constexpr (HI) {
+        constexpr int PZ[3] = {1, 0, 0}, PX[3] = {0, 1, 0};   // entries 3, 4, 5 of the six-product tables
+#pragma unroll
+        for (int t = 0; t < 3; ++t) {
+          if (j + 1 < TN && t < 2) fz[cur ^ 1][t] = fload(sZ + t * PLZ, LDZ, wn * 16 * TN + (j + 1) * 16);
+          if constexpr (!PC) {
+            if (t == 1) split_chunk(RA, m1 < me ? m1 : me, buf ^ 1, 0, j);
+            if (t == 2 && j < NCX) split_chunk(RA, m1 < me ? m1 : me, buf ^ 1, 1, j);
+          }
+          __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+          for (int i = 0; i < TK; ++i) acc[j][i] = mma(fz[cur][PZ[t]], fx[i][PX[t]], acc[j][i]);
+          __builtin_amdgcn_sched_barrier(0);
+        }
+      } else {
       constexpr int PZ[6] = {2, 0, 1, 1, 0, 0}, PX[6] = {0, 2, 1, 0, 1, 0};
 #pragma unroll
       for (int t = 0; t < 6; ++t) {
@@ -623,6 +697,7 @@ __global__ void __launch_bounds__(PC ? 512 : 256, PC ? 2 : 1) k_lin3r_dw(L32DwAr
           else acc[j][i] = mma(fz[cur][PZ[t]], fx[i][PX[t]], acc[j][i]);
         }
         __builtin_amdgcn_sched_barrier(0);
+      }
       }
     }
     if constexpr (!PC) RA = RB;
@@ -675,9 +750,10 @@ static inline int w3r_dw_pick_shape(int64_t N, int64_t K) {   // least padded ar
   }
   return best;
 }
-template <int TN, int TK>
+template <int TN, int TK, bool HI = false>
 static inline void w3r_launch_dw_shape(dim3 grid, hipStream_t stream, const L32DwArgs& a) {
-  constexpr int LDS = 2 * 2 * (3 * 32 * (32 * TN + 8) + 3 * 32 * (32 * TK + 8));
+  constexpr int NPL = HI ? 2 : 3;
+  constexpr int LDS = 2 * 2 * (NPL * 32 * (32 * TN + 8) + NPL * 32 * (32 * TK + 8));
   static std::mutex mu;
   static bool done[16] = {false};
   int dev = 0;
@@ -685,16 +761,23 @@ static inline void w3r_launch_dw_shape(dim3 grid, hipStream_t stream, const L32D
   {
     std::lock_guard<std::mutex> lk(mu);
     if (dev < 0 || dev >= 16 || !done[dev]) {
-      (void)hipFuncSetAttribute((const void*)(k_lin3r_dw<true, false, false, TN, TK>), hipFuncAttributeMaxDynamicSharedMemorySize, LDS);
-      (void)hipFuncSetAttribute((const void*)(k_lin3r_dw<false, false, false, TN, TK>), hipFuncAttributeMaxDynamicSharedMemorySize, LDS);
+      (void)hipFuncSetAttribute((const void*)(k_lin3r_dw<true, false, false, TN, TK, HI>), hipFuncAttributeMaxDynamicSharedMemorySize, LDS);
+      (void)hipFuncSetAttribute((const void*)(k_lin3r_dw<false, false, false, TN, TK, HI>), hipFuncAttributeMaxDynamicSharedMemorySize, LDS);
       if (dev >= 0 && dev < 16) done[dev] = true;
     }
   }
-  if (a.ymask) hipLaunchKernelGGL((k_lin3r_dw<true, false, false, TN, TK>), grid, dim3(256), LDS, stream, a);
-  else hipLaunchKernelGGL((k_lin3r_dw<false, false, false, TN, TK>), grid, dim3(256), LDS, stream, a);
+  if (a.ymask) hipLaunchKernelGGL((k_lin3r_dw<true, false, false, TN, TK, HI>), grid, dim3(256), LDS, stream, a);
+  else hipLaunchKernelGGL((k_lin3r_dw<false, false, false, TN, TK, HI>), grid, dim3(256), LDS, stream, a);
 }
+// "high" (L32DwArgs::high): the two-plane instantiations of the one-wave-per-SIMD form, gated or not; a row map keeps six products
+static inline bool w3r_dw_high(const L32DwArgs& a) { return a.high && !a.dy_rows; }
 static inline void w3r_launch_dw(dim3 grid, hipStream_t stream, const L32DwArgs& a, int shape = 0) {
-  if (shape == 1) { w3r_launch_dw_shape<7, 4>(grid, stream, a); return; }   // (no row map there: w3r_dw_ok with groups)
+  if (shape == 1) {   // (no row map there: w3r_dw_ok with groups)
+    if (w3r_dw_high(a)) w3r_launch_dw_shape<7, 4, true>(grid, stream, a);
+    else w3r_launch_dw_shape<7, 4>(grid, stream, a);
+    return;
+  }
+  if (w3r_dw_high(a)) { w3r_launch_dw_shape<5, 5, true>(grid, stream, a); return; }
   constexpr int LDS = 2 * 6 * W3D_PLANE * 2;
   static std::mutex mu;
   static bool done[16] = {false};

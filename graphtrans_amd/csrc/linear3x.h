@@ -12,6 +12,17 @@
 // replace eight v_mfma_f32_16x16x4_f32 (8 x 32 cycles): 2.7 x the matrix-pipe ceiling at fp32 accuracy.
 // Non-finite inputs: inf - inf = NaN in the split, i.e. an inf activation yields NaN where the exact kernel yields inf.
 //
+// "High" (compute == GT_COMPUTE_F32_HIGH, opt-in; ops.set_matmul_precision("high")): an operand counts as the sum of its first TWO planes,
+// a0 = bf16(a), a1 = bf16(a - a0) (round to nearest even: gt_pack_bf16 -- the planes w3_split_pair and the images already hold), and a
+// GEMM keeps the three products of order <= 2^-8, accumulated in the fp32 MFMA accumulators small terms first: (w1, a0), (w0, a1),
+// (w0, a0) = entries 3, 4, 5 of the PW / PA tables.  Each dropped product is at most 2^-16 |a||w|, the three together 3 * 2^-16 |a||w|:
+// relative L2 to float64 4.4e-6 on the test shapes (tests/test_hip_linear_high.py holds 2^-16 and pins the product set against a float64
+// evaluation of exactly these products).  Half the MFMAs; plane 2 of an image is not fetched (a third less LDS-DMA and LDS), the rows are
+// split two ways (w3_split_pair2).  bf16-stored rows without a gate (NPA == 1) would keep (w0, a0), (w1, a0); those forms are not
+// instantiated -- they, the GELU / row-map / LayerNorm-epilogue forms and k_lin3_dw keep six products (w3_high below; the contract of
+// "high" is one-sided: never less accurate than the three products).  The permission is a field of the call (L32Args::high, set from
+// LinFwd / LinBwd::high), the default instantiations (HI = false) are the code they were.
+//
 // Weights are split ONCE per step into an "image" (k_w3_image, all weights of a model in one launch): bf16 planes laid out in
 // the order the LDS wants them -- [k-step of 32][plane][16-row tile][1 KB: row r, 16-byte chunk (c ^ (r >> 1 & 3))] -- so a
 // k-step's tiles reach the LDS by global_load_lds_dwordx4 (LDS-DMA, lane-linear, no staging registers, no ds_write) and the
@@ -62,6 +73,12 @@ __device__ __forceinline__ void w3_split_pair(float lo, float hi, uint32_t& u1, 
   u3 = gt_pack_bf16(rl - __uint_as_float(u2 << 16), rh - __uint_as_float(u2 & 0xffff0000u));
 }
 
+// "high": the first two planes only (the same values as the first two of w3_split_pair)
+__device__ __forceinline__ void w3_split_pair2(float lo, float hi, uint32_t& u1, uint32_t& u2) {
+  u1 = gt_pack_bf16(lo, hi);
+  u2 = gt_pack_bf16(lo - __uint_as_float(u1 << 16), hi - __uint_as_float(u1 & 0xffff0000u));   // exact differences
+}
+
 __global__ void __launch_bounds__(256) k_w3_image(W3Jobs jobs) {
   int ji = 0;
   for (int i = 1; i < jobs.n; ++i)
@@ -95,13 +112,17 @@ typedef const __attribute__((address_space(1))) void w3_glb_void;
 
 // out[M][Nout] = epilogue(A[M][Kc] Wimg^T); L32Args: a / amask / bias / add1 / add2 / out / gout / M / Nout / Kc / lda / ldo /
 // act / inv_keep / thr / s0 / s1 / ncb as for k_lin32; w3 = the image, w3_ntp its tiles per plane
-template <typename TA, typename TO, int NT, int MT, int WBUF, bool MASK, bool GELU = false>
+// HI ("high"): two planes of each operand in the LDS (plane 2 of the image is not fetched) and the last three entries of the product
+// tables; fp32 rows only.
+template <typename TA, typename TO, int NT, int MT, int WBUF, bool MASK, bool GELU = false, bool HI = false>
 __global__ void __launch_bounds__(256, 2) k_lin3(L32Args a) {
+  static_assert(!HI || (sizeof(TA) == 4 && !GELU), "the three-product form: fp32 rows, no GELU epilogue");
   constexpr int BM = 32 * MT;                               // 2 x 2 waves, MT m-tiles per wave: 64 (MT = 2) or 128 rows (MT = 4)
   constexpr int AR = BM / 64;                               // rows per staging thread
-  constexpr int NPA = (sizeof(TA) == 2 && !MASK) ? 1 : 3;   // planes of the row operand (bf16 rows ARE their first plane)
+  constexpr int NPW = HI ? 2 : 3;                           // planes of the weight held per stage
+  constexpr int NPA = (sizeof(TA) == 2 && !MASK) ? 1 : NPW;   // planes of the row operand (bf16 rows ARE their first plane)
   constexpr int HT = NT / 2;                                // n-tiles per wave
-  constexpr int WSTAGE = 3 * NT * 1024, APLANE = BM * 64;
+  constexpr int WSTAGE = NPW * NT * 1024, APLANE = BM * 64;
   constexpr int PLD = HT * 16 + 4;                          // epilogue patch pitch (floats)
   extern __shared__ __attribute__((aligned(1024))) unsigned char smem3[];
   unsigned char* sA = smem3 + WBUF * WSTAGE;
@@ -224,11 +245,18 @@ __global__ void __launch_bounds__(256, 2) k_lin3(L32Args a) {
           }
         }
         uint32_t p1[4], p2[4], p3[4];
+        if constexpr (HI) {
+#pragma unroll
+          for (int e = 0; e < 4; ++e) w3_split_pair2(f[2 * e], f[2 * e + 1], p1[e], p2[e]);
+          *reinterpret_cast<uint4*>(dst) = make_uint4(p1[0], p1[1], p1[2], p1[3]);
+          *reinterpret_cast<uint4*>(dst + APLANE) = make_uint4(p2[0], p2[1], p2[2], p2[3]);
+        } else {
 #pragma unroll
         for (int e = 0; e < 4; ++e) w3_split_pair(f[2 * e], f[2 * e + 1], p1[e], p2[e], p3[e]);
         *reinterpret_cast<uint4*>(dst) = make_uint4(p1[0], p1[1], p1[2], p1[3]);
         *reinterpret_cast<uint4*>(dst + APLANE) = make_uint4(p2[0], p2[1], p2[2], p2[3]);
         *reinterpret_cast<uint4*>(dst + 2 * APLANE) = make_uint4(p3[0], p3[1], p3[2], p3[3]);
+        }
       }
     }
   };
@@ -237,9 +265,9 @@ __global__ void __launch_bounds__(256, 2) k_lin3(L32Args a) {
     const unsigned char* src = img + (int64_t)ks * 3 * plane_stride;
     unsigned char* dstb = smem3 + buf * WSTAGE;
 #pragma unroll
-    for (int i0 = 0; i0 < 3 * NT; i0 += 4) {
+    for (int i0 = 0; i0 < NPW * NT; i0 += 4) {
       const int i = i0 + wid;
-      if (i < 3 * NT) {
+      if (i < NPW * NT) {
         const int p = i / NT, j = i % NT;
         __builtin_amdgcn_global_load_lds((w3_glb_void*)(src + p * plane_stride + (int64_t)j * 1024), (w3_lds_void*)(dstb + i * 1024), 16, 0, 0);
       }
@@ -282,20 +310,20 @@ __global__ void __launch_bounds__(256, 2) k_lin3(L32Args a) {
       }
 #pragma unroll
     for (int jp = 0; jp < HT; jp += 2) {
-      bf16x8_t fw[2][3];
+      bf16x8_t fw[2][NPW];
 #pragma unroll
       for (int jj = 0; jj < 2; ++jj)
         if (jp + jj < HT) {
 #pragma unroll
-          for (int p = 0; p < 3; ++p) {
+          for (int p = 0; p < NPW; ++p) {
             if constexpr (W3_ABL & 64) fw[jj][p] = __builtin_bit_cast(bf16x8_t, make_uint4(ks + jp, p + jj, lane, 9));
             else fw[jj][p] = *reinterpret_cast<const bf16x8_t*>(sW + (p * NT + wn * HT + jp + jj) * 1024);
           }
         }
-      // the six products, small terms first; each round touches 2 x MT independent accumulators
+      // the six products, small terms first; each round touches 2 x MT independent accumulators ("high": the last three)
       constexpr int PW[6] = {2, 0, 1, 1, 0, 0}, PA[6] = {0, 2, 1, 0, 1, 0};
 #pragma unroll
-      for (int t = 0; t < 6; ++t) {
+      for (int t = HI ? 3 : 0; t < 6; ++t) {
         if (PA[t] < NPA) {
 #pragma unroll
           for (int jj = 0; jj < 2; ++jj)
@@ -447,9 +475,9 @@ __global__ void __launch_bounds__(256, 2) k_lin3(L32Args a) {
   }
 }
 
-template <typename TA, typename TO, int NT, int MT, int WBUF, bool MASK, bool GELU>
+template <typename TA, typename TO, int NT, int MT, int WBUF, bool MASK, bool GELU, bool HI = false>
 void w3_launch_one(dim3 grid, hipStream_t stream, const L32Args& a) {
-  constexpr int LDS = WBUF * 3 * NT * 1024 + 3 * 32 * MT * 64;
+  constexpr int LDS = WBUF * (HI ? 2 : 3) * NT * 1024 + (HI ? 2 : 3) * 32 * MT * 64;
   static std::mutex mu;   // per instantiation: the > 64 KB dynamic-LDS opt-in is set once per device (C-ABI: one-time queries guarded)
   static bool done[16] = {false};
   int dev = 0;
@@ -457,11 +485,11 @@ void w3_launch_one(dim3 grid, hipStream_t stream, const L32Args& a) {
   {
     std::lock_guard<std::mutex> lk(mu);
     if (dev < 0 || dev >= 16 || !done[dev]) {
-      (void)hipFuncSetAttribute((const void*)(k_lin3<TA, TO, NT, MT, WBUF, MASK, GELU>), hipFuncAttributeMaxDynamicSharedMemorySize, LDS);
+      (void)hipFuncSetAttribute((const void*)(k_lin3<TA, TO, NT, MT, WBUF, MASK, GELU, HI>), hipFuncAttributeMaxDynamicSharedMemorySize, LDS);
       if (dev >= 0 && dev < 16) done[dev] = true;
     }
   }
-  hipLaunchKernelGGL((k_lin3<TA, TO, NT, MT, WBUF, MASK, GELU>), grid, dim3(256), LDS, stream, a);
+  hipLaunchKernelGGL((k_lin3<TA, TO, NT, MT, WBUF, MASK, GELU, HI>), grid, dim3(256), LDS, stream, a);
 }
 
 #ifndef W3_FORCE_MT
@@ -480,8 +508,15 @@ static inline int w3_pick_mt(int64_t M, int ncb) {
   return gt_cdiv(M, 128) * ncb >= 384 ? 4 : 2;
 }
 
+// "high" (L32Args::high) runs three products in k_lin3: fp32 rows in and out with bias / ReLU / gate / addends (grouped or not, a
+// virtual concatenation included); the GELU, row-map and LayerNorm-epilogue forms and bf16 rows on either side keep six
+static inline bool w3_high(int ta, int to, const L32Args& a) {
+  return a.high && ta == GT_F32 && to == GT_F32 && a.act != 2 && !a.gout && !a.a_rows && !a.out_rows && !a.ln_out;
+}
+
 template <bool MASK>
 void w3_launch(int ta, int to, hipStream_t stream, L32Args& a) {
+  const bool hi = w3_high(ta, to, a);
   if (a.groups > 1 && a.Nout <= 96 && ta == GT_F32 && to == GT_F32 && a.act != 2) {
     // a grouped launch of narrow GEMMs (the PNA pre stack's dX: 136 -> 68 columns per tower): 6 n-tiles, 64 rows, one W buffer =
     // 30 KB of LDS and 107 registers instead of 48 KB and 185 -- it runs beside the post stack's weight-gradient kernel (138 KB of LDS on
@@ -490,7 +525,8 @@ void w3_launch(int ta, int to, hipStream_t stream, L32Args& a) {
     a.ncb = 1;
     a.w3_ntp = (int)w3_ntp(a.Nout);
     dim3 grid((unsigned)(gt_cdiv(gt_cdiv(a.M, 64), 8) * 8), (unsigned)a.groups);
-    w3_launch_one<float, float, 6, 2, 1, MASK, false>(grid, stream, a);
+    if (hi) w3_launch_one<float, float, 6, 2, 1, MASK, false, true>(grid, stream, a);
+    else w3_launch_one<float, float, 6, 2, 1, MASK, false>(grid, stream, a);
     return;
   }
   const int nt = w3_pick_nt(a.Nout);
@@ -516,7 +552,12 @@ void w3_launch(int ta, int to, hipStream_t stream, L32Args& a) {
     if (nt == 10) GT_W3_MT(TA_, TO_, 10, false);                 \
     else GT_W3_MT(TA_, TO_, 8, false);                           \
   } while (0)
-  if (ta == GT_F32 && to == GT_F32) GT_W3_GO(float, float);
+  if (hi) {
+    if (nt == 10 && mt == 4) w3_launch_one<float, float, 10, 4, W3_WB_MT4, MASK, false, true>(grid, stream, a);
+    else if (nt == 10) w3_launch_one<float, float, 10, 2, W3_WB_MT2, MASK, false, true>(grid, stream, a);
+    else if (mt == 4) w3_launch_one<float, float, 8, 4, W3_WB_MT4, MASK, false, true>(grid, stream, a);
+    else w3_launch_one<float, float, 8, 2, W3_WB_MT2, MASK, false, true>(grid, stream, a);
+  } else if (ta == GT_F32 && to == GT_F32) GT_W3_GO(float, float);
   else if (ta == GT_F32) GT_W3_GO(float, gt_bf16);
   else if (to == GT_F32) GT_W3_GO(gt_bf16, float);
   else GT_W3_GO(gt_bf16, gt_bf16);

@@ -1,6 +1,9 @@
 // linear_call.h — the call records of the Linear GEMM dispatchers (linear.hip).  One record carries everything one GEMM call was asked
 // for: the argument list of gt_linear_fwd_grouped / gt_linear_bwd_grouped, in its order (`LinBwd c{x_dtype, ..., stream};` fills it, every
 // option off), then the options the variant entry points add.  The public entry points fill a record and call lin_fwd / lin_bwd; so do
+// `compute` is a gt_compute value: lin_fwd / lin_bwd normalise it ONCE, on their own copy of the record -- GT_COMPUTE_F32_HIGH becomes
+// GT_F32 with `high` set -- so every `compute == GT_F32` test of the dispatchers sees fp32 semantics and the permission to run three
+// products travels with the call (into L32Args / L32DwArgs), never through a process-wide option.
 // the library's own layers (layers.hip, model.hip), which never go through the set-before-the-call entry points (gt_linear_set_rows*,
 // gt_linear_bwd_bnstats, gt_linear_bwd_bcast: the outside ABI only).
 #pragma once
@@ -30,6 +33,7 @@ struct LinFwd {
   const void* x2;   // contraction columns [x_split, K) of the row operand come from this matrix, pitch ldx2 (gt_linear_fwd_cat2)
   int64_t x_split, ldx2;
   LinRowMap map;
+  bool high;        // three bf16 products per fp32 product allowed (set by lin_fwd from compute == GT_COMPUTE_F32_HIGH, which it turns into GT_F32)
 };
 struct LinBwd {
   int x_dtype, y_dtype, compute;
@@ -61,6 +65,7 @@ struct LinBwd {
   void* dx2;
   int64_t x_split, ldx2;
   LinRowMap map;
+  bool high;               // as LinFwd::high (set by lin_bwd)
 };
 __attribute__((visibility("hidden"))) int lin_fwd(const LinFwd& f);
 __attribute__((visibility("hidden"))) int lin_bwd(const LinBwd& c);

@@ -382,7 +382,7 @@ extern "C" int gt_model_prepare(const gt_model* m, const gt_model_batch* b, void
   c->o_ws = a.take(ws);
   c->o_ws2 = a.take(ws2);
   const bool have_imgs = b->use_w3 != 0;
-  c->want_wt = (m->conv != GT_CONV_PNA && b->will_bwd && c->compute == GT_F32 && N >= 1024 && (!have_imgs || (!m->has_vn && m->conv == GT_CONV_GCN))) ? 1 : 0;
+  c->want_wt = (m->conv != GT_CONV_PNA && b->will_bwd && gt_compute_base(c->compute) == GT_F32 && N >= 1024 && (!have_imgs || (!m->has_vn && m->conv == GT_CONV_GCN))) ? 1 : 0;
   if (c->want_wt) {
     for (int l = 0; l < L; ++l) c->o_wt[l] = a.take((size_t)(m->conv == GT_CONV_GIN ? 2 : 1) * 2 * D * D * 4);
     c->o_g2t_wt = a.take((size_t)d * Kc * 4);

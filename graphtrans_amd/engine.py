@@ -994,7 +994,8 @@ class _FusedModel(torch.autograd.Function):
         # (layers.hip: dtype == bf16 ? bf16 : compute), i.e. (fp32, bf16 tokens) is the mixed mode of bench.py
         bf16_mm = ops.get_matmul_dtype() == torch.bfloat16
         tok_bf16 = enc.compute_dtype == torch.bfloat16
-        bt.training, bt.compute, bt.tdt = int(training), (GT_BF16 if bf16_mm else GT_F32), (GT_BF16 if tok_bf16 else GT_F32)
+        # (ops.set_matmul_precision is read here, at every forward; the prepared context carries it to this forward's backward)
+        bt.training, bt.compute, bt.tdt = int(training), ops.f32_compute_code(), (GT_BF16 if tok_bf16 else GT_F32)
         will_bwd = bool(ctx.needs_input_grad[0])
         bt.will_bwd = int(will_bwd)
         # exact-fp32 GEMM mode: the big-M linears run as bf16x6 on the bf16 matrix pipe on images of their weights; bf16 token rows:

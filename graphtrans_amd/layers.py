@@ -97,7 +97,7 @@ def _split(flat, params):
 
 def _compute_code():
     from . import ops
-    return GT_BF16 if ops.get_matmul_dtype() == torch.bfloat16 else GT_F32
+    return ops.f32_compute_code()   # GT_F32, GT_BF16 or GT_COMPUTE_F32_HIGH (ops.set_matmul_precision)
 
 
 def _f32c(p):

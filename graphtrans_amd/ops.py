@@ -11,7 +11,7 @@ import os
 import torch
 
 from . import _lib
-from ._lib import GT_BF16, GT_CONV_GCN, GT_CONV_GIN, GT_EDGE_DENSE, GT_EDGE_LINEAR, GT_EDGE_NONE, GT_EDGE_TABLES, GT_F32
+from ._lib import GT_BF16, GT_COMPUTE_F32_HIGH, GT_CONV_GCN, GT_CONV_GIN, GT_EDGE_DENSE, GT_EDGE_LINEAR, GT_EDGE_NONE, GT_EDGE_TABLES, GT_F32
 from .graph import _ptr, _stream
 
 
@@ -538,6 +538,41 @@ def get_matmul_dtype():
     return _MATMUL_DTYPE
 
 
+def _env_matmul_precision():
+    v = os.environ.get("GT_F32_PRECISION", "highest").strip().lower() or "highest"
+    if v not in ("highest", "high"):
+        raise ValueError("GT_F32_PRECISION must be 'highest' or 'high', got %r" % v)
+    return v
+
+
+_MATMUL_PRECISION = _env_matmul_precision()   # read once, at import
+
+
+def set_matmul_precision(precision):
+    """Precision of the fp32-COMPUTED linears (get_matmul_dtype() == torch.float32).  "highest" (the default): fp32-accurate,
+    six bf16 products per fp32 product on bound weight images.  "high": every fp32 operand counts as the sum of its first two
+    bf16 planes and the GEMMs that have a three-product kernel keep (w1, a0), (w0, a1), (w0, a0): about 16 significand bits, half
+    the matrix-pipe work (torch.set_float32_matmul_precision("high")'s two-bf16 description, not TF32).  Everything without such a
+    kernel computes as under "highest"; set_matmul_dtype(torch.bfloat16) wins over it.  Read at every forward; a backward uses
+    the precision of its forward.  Returns the previous value."""
+    global _MATMUL_PRECISION
+    if precision not in ("highest", "high"):
+        raise ValueError("matmul precision must be 'highest' or 'high', got %r" % (precision,))
+    prev, _MATMUL_PRECISION = _MATMUL_PRECISION, precision
+    return prev
+
+
+def get_matmul_precision():
+    return _MATMUL_PRECISION
+
+
+def f32_compute_code():
+    """The gt_compute value of an fp32-stored GEMM under the current matmul dtype and precision."""
+    if _MATMUL_DTYPE == torch.bfloat16:
+        return GT_BF16
+    return GT_COMPUTE_F32_HIGH if _MATMUL_PRECISION == "high" else GT_F32
+
+
 class _Linear(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, weight, bias, act, dropout_p, seed, compute, out_dtype, ldy):
@@ -573,7 +608,7 @@ class _Linear(torch.autograd.Function):
         N = w32.shape[0]
         need_x, need_w, need_b = ctx.needs_input_grad[0], ctx.needs_input_grad[1], bdt is not None and ctx.needs_input_grad[2]
         ydt = ymask.dtype if ymask is not None else (dy.dtype if dy.dtype in (torch.float32, torch.bfloat16) else torch.float32)
-        if compute == GT_F32:
+        if compute != GT_BF16:
             ydt = torch.float32
         if ldy != N:
             dy2 = _padded_rows(dy.reshape(M, N).to(ydt), ldy)
@@ -626,10 +661,10 @@ def linear(x, weight, bias=None, act=None, dropout_p=0.0, seed=0, out_dtype=None
     if x.dtype == torch.bfloat16:
         compute = GT_BF16
     else:
-        compute = GT_BF16 if _MATMUL_DTYPE == torch.bfloat16 else GT_F32
+        compute = f32_compute_code()
     if out_dtype is None:
         out_dtype = x.dtype
-    if compute == GT_F32 and out_dtype != torch.float32:
+    if compute != GT_BF16 and out_dtype != torch.float32:
         raise ValueError("fp32 compute writes fp32")
     if act not in (None, "relu", "gelu"):
         raise ValueError(act)
@@ -949,5 +984,5 @@ def tower_linear(x, weight, bias=None):
     launch (gt_linear_*_grouped, grid.y = tower) on column slices (no transposes, no per-tower copies).  K and Nout multiples of 4 (8 for bf16)."""
     if x.dim() != 3 or weight.dim() != 3 or x.shape[1] != weight.shape[0] or x.shape[2] != weight.shape[2]:
         raise ValueError("tower_linear: x (M, T, K), weight (T, Nout, K)")
-    compute = GT_BF16 if (x.dtype == torch.bfloat16 or _MATMUL_DTYPE == torch.bfloat16) else GT_F32
+    compute = GT_BF16 if x.dtype == torch.bfloat16 else f32_compute_code()
     return _TowerLinear.apply(x, weight, bias, compute)

@@ -38,6 +38,12 @@ enum gt_status {
 };
 
 enum gt_dtype { GT_F32 = 0, GT_BF16 = 1 };
+/* Every `compute` argument and descriptor field: how the products of a GEMM are formed.  0 and 1 are the gt_dtype values.
+ * GT_COMPUTE_F32_HIGH is fp32 compute (fp32 storage, every rule of GT_F32 holds) that ALLOWS the big-M GEMMs on bound weight
+ * images to treat each fp32 operand as the sum of its first two bf16 planes and to keep three of the six plane products (see
+ * "fp32-accurate GEMMs on the bf16 matrix pipe" below).  One-sided: a GEMM under "high" is never less accurate than those three
+ * products, and wherever no three-product kernel takes the call the result is bit-identical to GT_COMPUTE_F32. */
+enum gt_compute { GT_COMPUTE_F32 = 0, GT_COMPUTE_BF16 = 1, GT_COMPUTE_F32_HIGH = 2 };
 enum gt_conv { GT_CONV_GCN = 0, GT_CONV_GIN = 1, GT_CONV_PNA = 2 /* the whole-model driver's third layer kind (gt_pna_layer) */ };
 enum gt_edge_mode {
   GT_EDGE_NONE = 0,   /* edge embedding == 0          (dataset/tud.py:67-71)            */
@@ -432,8 +438,9 @@ int gt_layernorm_bwd_finish(const float* part, int nblk, int64_t dim, float* dwe
  *        else dz = dy;  dx = dz weight [+ dx_add1 + dx_add2];  dweight = dz^T x;  dbias = colsum(dz)
  *        (any output may be NULL; dx_add* are optional [M][K] addends in x's storage type)
  * weight/bias and their gradients are fp32 (master weights are converted while staging: no cast
- * pass).  x_dtype / y_dtype: storage of x (and dx) / y (and dy); compute: GT_BF16
- * (v_mfma_f32_16x16x32_bf16) or GT_F32 (v_mfma_f32_16x16x4_f32, needs fp32 storage).
+ * pass).  x_dtype / y_dtype: storage of x (and dx) / y (and dy); compute (gt_compute): GT_BF16
+ * (v_mfma_f32_16x16x32_bf16), GT_F32 (v_mfma_f32_16x16x4_f32, needs fp32 storage) or GT_COMPUTE_F32_HIGH
+ * (GT_F32 that allows three bf16 products per fp32 product on bound weight images: gt_linear_products).
  * N % 4 == 0 and K % 4 == 0.  Fused dropout requires act == relu.  Deterministic.
  * dX of a long contraction with few output tiles (N >= 2048) is split over N into fp32 partials.
  */
@@ -517,7 +524,23 @@ int gt_transpose(const float* in /* [N][K] */, float* out /* [K][N] */, int64_t 
  * models/gnn_transformer.py:69-70).  An fp32 value is EXACTLY the sum of three bf16 values; keeping the six operand-plane
  * products down to relative 2^-16 reproduces the fp32 GEMM to accumulation order at 2.7 x the fp32-MFMA ceiling.  A weight is
  * split once per optimizer step into an "image" (bf16 planes in LDS order); bound images reroute the big-M exact-fp32 GEMMs of
- * gt_linear_fwd* / gt_linear_bwd* (compute == GT_F32, M >= 1024, one group) to the bf16x6 kernel. */
+ * gt_linear_fwd* / gt_linear_bwd* (compute == GT_F32, M >= 1024, one group) to the bf16x6 kernel.
+ *
+ * "high" (compute == GT_COMPUTE_F32_HIGH): an fp32 operand a gives the planes a0 = bf16(a), a1 = bf16(a - a0) (round to nearest
+ * even; the first two planes of the three-way split and of the images), and a GEMM keeps the three products of order <= 2^-8,
+ * (w1, a0), (w0, a1), (w0, a0), accumulated in fp32 in that order.  Each of the three dropped products is at most 2^-16 |a||w|:
+ * about 16 significand bits, half the matrix-pipe work.  This is the two-bf16 split that PyTorch's
+ * set_float32_matmul_precision("high") describes, not TF32's bits.  Plane 2 of an image is simply not fetched: the images are the
+ * same.  Three products run in k_lin3r (forward and dX), k_lin3r_dw without a row map, and k_lin3 with fp32 rows in and out
+ * (bias / ReLU / gate / addends, grouped or concatenated operands); the GELU, row-map and LayerNorm-epilogue forms of k_lin3, its
+ * bf16-row forms and k_lin3_dw keep six.  One call changes kernel under "high": the WEIGHT GRADIENT of a short-M call (M <= 512) on a
+ * bound weight runs k_lin3r_dw with three products from 32 rows on (one whole stage of that kernel) instead of the fp32 short-M kernel,
+ * which has no three-product form.  Everything else (no image bound, forward and dX below 1024 rows, dW below 32 rows, the heads
+ * kernels, attention) computes exactly as under GT_F32. */
+/* How many bf16 products per fp32 product a PLAIN call (no row map, gate, GELU or other per-call option) of gt_linear_fwd /
+ * gt_linear_bwd would run under this host thread's current image bindings: 0 = not a split kernel, 6 or 3.
+ * which: 0 forward, 1 dX, 2 dW. */
+int gt_linear_products(int which, int x_dtype, int y_dtype, int compute, const float* weight, int64_t M, int64_t N, int64_t K);
 /* JK = "cat" without its copy (torch.cat([h_list[0], h_list[-1]], 1), modules/gnn_module.py:104-105, feeding gnn2transformer,
  * models/gnn_transformer.py:92): the GEMM reads its row operand from two matrices side by side and its backward writes the two
  * gradients where their consumers read them.  Only on weights whose images are bound (ask gt_linear_cat2_ok first). */
@@ -690,7 +713,7 @@ int gt_bce_masked_bwd(const float* logits, const float* target, const float* out
  */
 typedef struct gt_encoder_layer {  /* torch nn.TransformerEncoderLayer, post-norm, ReLU or GELU FFN */
   int64_t rows, d_model, ffn;
-  int32_t nhead, dtype /* token storage */, compute /* fp32 storage only: GT_F32 | GT_BF16 */, training;
+  int32_t nhead, dtype /* token storage */, compute /* fp32 storage only: gt_compute */, training;
   const int32_t* seq_desc;
   int64_t num_seqs, row_stride, max_npos;
   const int32_t* work_items; /* optional attention tile list, see gt_attn_fwd */
@@ -978,7 +1001,7 @@ typedef struct gt_model_batch {
   int64_t depth_stride;
   const void* edge_attr;
   const int32_t *zeros_B, *ident_B, *ptr01;   /* [B] zeros, [B] 0..B-1, {0, B} (device, int32) */
-  int32_t training, compute /* GT_F32 | GT_BF16: the fp32-stored GEMMs */, tdt /* token rows */, will_bwd;
+  int32_t training, compute /* gt_compute: the fp32-stored GEMMs */, tdt /* token rows */, will_bwd;
   int32_t use_w3 /* 0 none, 1 gt_model.w3, 2 gt_model.w3_enc */, use_w1, sync_bn /* gt_bn_sync_set hook installed */, pad2_;
   float gnn_p, enc_p;
   uint64_t gnn_seed, enc_seed;

@@ -1,18 +1,23 @@
 #!/usr/bin/env python
-"""k_lin3r (rows straight into MFMA fragments, csrc/linear3r.h) against k_lin3 (both operands through the LDS): forward and un-gated dX
-on the shapes of the benchmarked configurations.  usage: python tools/gemm3r_bench.py   (GPU box; A/B against another build: GT_LIB_PATH)"""
+"""The split GEMMs on bound weight images alone on the chip: k_lin3r (rows straight into MFMA fragments, csrc/linear3r.h; M >= 12 288) or
+k_lin3 (both operands through the LDS) forward, un-gated dX, dX with an addend, and the weight gradient (k_lin3r_dw + its reduce), under
+"highest" (six bf16 products per fp32 product) and "high" (three: compute = GT_COMPUTE_F32_HIGH), alternating in the same process.
+usage: python tools/gemm3r_bench.py [--precision highest|high|both] [--shapes MxNxK,...] [--rounds R]
+(GPU box; A/B against another build: GT_LIB_PATH)"""
+import argparse
 import os
-import subprocess
 import sys
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tests"))
 import torch
 
+from graphtrans_amd import _lib
+from graphtrans_amd.graph import _stream
 from graphtrans_amd.w3 import W3Images
-from test_hip_linear3x import bwd_all, dx_of, fwd
 
 DEV = "cuda:0"
+CODES = {"highest": 0, "high": 2}   # enum gt_compute
+DEFAULT_SHAPES = [(31598, 300, 300), (131072, 256, 256), (16000, 272, 272), (31598, 600, 300), (31598, 300, 600), (12800, 300, 300), (6700, 600, 300)]
 
 
 def timeit(fn, n=100):
@@ -29,22 +34,67 @@ def timeit(fn, n=100):
     return 1e3 * s.elapsed_time(e) / n
 
 
+def _p(t):
+    return None if t is None else t.data_ptr()
+
+
+class Gemm:
+    def __init__(self, M, N, K):
+        self.M, self.N, self.K = M, N, K
+        self.x = torch.randn(M, K, device=DEV)
+        self.W = torch.randn(N, K, device=DEV) / K ** 0.5
+        self.b = torch.randn(N, device=DEV)
+        self.dy = torch.randn(M, N, device=DEV)
+        self.a1 = torch.randn(M, K, device=DEV)
+        self.y, self.dx = torch.empty(M, N, device=DEV), torch.empty(M, K, device=DEV)
+        self.dw, self.db = torch.empty(N, K, device=DEV), torch.empty(N, device=DEV)
+        self.ws_bytes = _lib.lib().gt_linear_bwd_workspace_bytes(0, M, N, K)
+        self.ws = torch.empty(self.ws_bytes, dtype=torch.uint8, device=DEV)
+        self.imgs = W3Images([self.W])
+        self.imgs.build()
+
+    def fwd(self, c):
+        _lib.launch("gt_linear_fwd_ld2", 0, 0, c, _p(self.x), _p(self.W), _p(self.b), _p(self.y), self.M, self.N, self.K, self.K, self.N, 0, 0.0, 0, _stream())
+
+    def bwd(self, c, dx, dw, add=None):
+        _lib.launch("gt_linear_bwd_ld2", 0, 0, c, _p(self.x) if dw else None, _p(self.W), _p(self.dy), None, _p(add), None, _p(self.dx) if dx else None,
+                    _p(self.dw) if dw else None, _p(self.db) if dw else None, self.M, self.N, self.K, self.K, self.N, 0.0, _p(self.ws), self.ws_bytes, _stream())
+
+    def products(self, which, c):
+        return _lib.lib().gt_linear_products(which, 0, 0, c, _p(self.W), self.M, self.N, self.K)
+
+
 def main():
-    tag = "k_lin3r"
-    for M, N, K in [(31598, 300, 300), (131072, 256, 256), (16000, 272, 272), (31598, 600, 300), (31598, 300, 600), (12800, 300, 300)]:
-        x = torch.randn(M, K, device=DEV)
-        W = torch.randn(N, K, device=DEV) / K ** 0.5
-        b = torch.randn(N, device=DEV)
-        dy = torch.randn(M, N, device=DEV)
-        a1 = torch.randn(M, K, device=DEV)
-        imgs = W3Images([W])
-        imgs.build()
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--precision", choices=["highest", "high", "both"], default="both")
+    ap.add_argument("--shapes", default="")
+    ap.add_argument("--rounds", type=int, default=3, help="alternating rounds per shape; the median is reported with min .. max")
+    a = ap.parse_args()
+    shapes = [tuple(int(v) for v in s.split("x")) for s in a.shapes.split(",") if s] or DEFAULT_SHAPES
+    precisions = ["highest", "high"] if a.precision == "both" else [a.precision]
+    for M, N, K in shapes:
+        g = Gemm(M, N, K)
         fl = 2.0 * M * N * K
-        t = timeit(lambda: fwd(x, W, b, imgs))
-        d = timeit(lambda: dx_of(x, W, dy, None, None, None, imgs))
-        da = timeit(lambda: dx_of(x, W, dy, None, a1, None, imgs))
-        dwt = timeit(lambda: bwd_all(x, W, dy, None, imgs), n=50)   # dX + dW + db + reduce
-        print(f"{tag} {M:7d} x {N:4d} x {K:4d}: fwd {t:6.1f} us ({fl / t / 1e6:6.1f} TF, {fl / t / 1e6 / 416.7:.3f} of bf16x6)  dX {d:6.1f} us  dX+addend {da:6.1f} us  dX+dW+db+reduce {dwt:6.1f} us (dW part ~{dwt - d:5.1f}, {fl / max(dwt - d, 1e-3) / 1e6 / 416.7:.3f})", flush=True)
+        forms = [("fwd", lambda c: g.fwd(c), 0), ("dX", lambda c: g.bwd(c, True, False), 1), ("dX+addend", lambda c: g.bwd(c, True, False, g.a1), 1),
+                 ("dW+db+reduce", lambda c: g.bwd(c, False, True), 2)]
+        times = {(f, p): [] for f, _, _ in forms for p in precisions}
+        with g.imgs.bound():
+            for _ in range(a.rounds):
+                for f, fn, _ in forms:
+                    for p in precisions:   # the two precisions back to back: same clocks, same neighbours
+                        times[(f, p)].append(timeit(lambda: fn(CODES[p]), n=50 if f.startswith("dW") else 100))
+            prods = {(f, p): g.products(which, CODES[p]) for f, _, which in forms for p in precisions}
+        for f, _, _ in forms:
+            row = []
+            for p in precisions:
+                t = sorted(times[(f, p)])
+                med = t[len(t) // 2]
+                row.append(f"{p} ({prods[(f, p)]} products) {med:6.1f} us [{t[0]:.1f} .. {t[-1]:.1f}] {fl / med / 1e6:6.1f} TF")
+            ratio = ""
+            if len(precisions) == 2:
+                h6, h3 = sorted(times[(f, "highest")]), sorted(times[(f, "high")])
+                ratio = f"  high / highest = {h3[len(h3) // 2] / h6[len(h6) // 2]:.3f}"
+            print(f"{M:7d} x {N:4d} x {K:4d} {f:13s}: " + "   ".join(row) + ratio, flush=True)
 
 
 if __name__ == "__main__":
