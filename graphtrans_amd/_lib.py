@@ -91,6 +91,7 @@ SIGNATURES = {
     "gt_linear_set_rows": (_i, [_p]),
     "gt_linear_rows_layernorm_ok": (_i, [_i64]),
     "gt_linear_set_rows_layernorm": (_i, [_p, _p, _p, _f, _p, _p, _p]),
+    "gt_linear_set_rows_add": (_i, [_p, _p, _i64]),
     "gt_linear_fwd_ld": (_i, [_i, _i, _i, _p, _p, _p, _p, _i64, _i64, _i64, _i64, _i, _f, _u64, _p]),
     "gt_linear_bwd_ld": (_i, [_i, _i, _i, _p, _p, _p, _p, _p, _p, _p, _p, _p, _i64, _i64, _i64, _i64, _f, _p, _sz, _p]),
     "gt_adamw_chunk_elems": (_i, []),
@@ -210,6 +211,8 @@ SIGNATURES = {
     "gt_model_forward": (_i, [_p, _p, _p, _p, _p]),
     "gt_model_backward": (_i, [_p, _p, _p, _p, _p, _i, _p]),
     "gt_seq_gather_cls32": (_i, [_i, _p, _p, _p, _p, _i64, _i64, _i64, _i, _i64, _p, _p]),
+    "gt_seq_positions": (_i, [_p, _p, _p, _i, _i64, _i64, _p, _p, _p]),
+    "gt_seq_gather_add": (_i, [_i, _i, _p, _p, _p, _p, _i64, _p, _p, _p, _i64, _i64, _i64, _i, _i64, _p, _p, _p]),
     "gt_colsum_f32": (_i, [_i, _p, _i64, _i64, _p, _p]),
     "gt_attn_head_dim_ok": (_i, [_i, _i64, _i]),
     "gt_attn_fwd": (_i, [_i, _p, _p, _p, _i64, _i64, _i, _p, _i64, _i64, _i64, _p, _i64, _p, _p, _f, _f, _f, _u64, _p]),

@@ -896,7 +896,7 @@ void w32_launch_dw_nt(int nt, dim3 grid, hipStream_t stream, const L32DwArgs& a)
 
 
 // ---- per-call requests of the outside ABI -----------------------------------------------------------------------------------------
-// gt_linear_set_rows, gt_linear_set_rows_layernorm, gt_linear_bwd_bnstats and gt_linear_bwd_bcast have no call of their own: what they
+// gt_linear_set_rows, gt_linear_set_rows_layernorm, gt_linear_set_rows_add, gt_linear_bwd_bnstats and gt_linear_bwd_bcast have no call of their own: what they
 // ask for waits here, per host thread, for the next public gt_linear_fwd* / gt_linear_bwd* call, which moves it into its record
 // (take_map / take_bwd: the only readers) -- only the request fields of this record are ever set.  The dispatchers below and the
 // library's own layers never see it: they pass records.
@@ -1000,6 +1000,10 @@ bool fwd_wide(const LinFwd& f, const LinArgs& a, int& rc) {
       w.ln_w = f.map.ln_w; w.ln_b = f.map.ln_b; w.ln_out = f.map.ln_out; w.ln_mean = f.map.ln_mean; w.ln_rstd = f.map.ln_rstd;
       w.ln_eps = f.map.ln_eps;
     }
+    if (f.map.add_table) {
+      if (f.act == 2) return fail("gt_linear_set_rows_add: not with the GELU epilogue");
+      w.add_tab = f.map.add_table; w.add_idx = f.map.add_idx; w.add_ld = f.map.add_ld;
+    }
   }
   const bool on_rows_kernel = w.w3 && w3r_ok(f.x_dtype, f.y_dtype, w);
   GtProfScope pk__(GT_PROF_GEMM_KERNEL, on_rows_kernel ? "k_lin3r[fwd]" : (w.w3 ? "k_lin3[fwd]" : "k_lin32[fwd]"), stream, LIN_DIMS(f));
@@ -1042,6 +1046,8 @@ int lin_fwd(const LinFwd& f_) {
   f.compute = gt_compute_base(f.compute);
   LIN_CHECK_ARG(fn, !f.map.rows || (f.groups == 1 && rows_eligible(f.compute, f.x_dtype, f.y_dtype, f.weight, f.M, f.N, f.K)),
                 "gt_linear_set_rows: this GEMM does not take a row map (ask gt_linear_rows_ok)");
+  LIN_CHECK_ARG(fn, !f.map.add_table || (f.map.rows && f.map.add_idx && f.map.add_ld >= f.N && f.map.add_ld % 4 == 0 && ((uintptr_t)f.map.add_table & 15) == 0),
+                "gt_linear_set_rows_add: the addend rides on a row map (gt_linear_set_rows*); fp32 table, 16-byte aligned, pitch >= N and a multiple of 4");
   int rc = check_call(fn, "gt_linear_fwd", f.x_dtype, f.y_dtype, f.compute, f.M, f.N, f.K, f.ldx, f.ldy, f.x2 ? f.x_split : f.K, f.groups,
                       f.x_group_stride, f.y_group_stride);
   if (rc) return rc;
@@ -1569,6 +1575,7 @@ int lin_bwd(const LinBwd& c_) {
     gt_set_error("gt_linear_bwd_bcast: this call does not run on the register-row kernel (ask gt_linear_bwd_bcast_ok)");
     return GT_ERR_UNSUPPORTED;
   }
+  LIN_CHECK_ARG(fn, !c.map.add_table, "gt_linear_set_rows_add: forward only (a constant addend has no backward)");
   LIN_CHECK_ARG(fn, !c.map.rows || (c.groups == 1 && !c.y_for_mask && !c.bn_part && !c.map.ln_out &&
                                     rows_eligible(c.compute, c.x_dtype, c.y_dtype, c.weight, c.M, c.N, c.K)),
                 "gt_linear_set_rows: this GEMM does not take a row map (ask gt_linear_rows_ok)");
@@ -1731,7 +1738,17 @@ extern "C" int gt_linear_rows_layernorm_ok(int64_t N) { return (N > 0 && N % 16 
 extern "C" int gt_linear_set_rows_layernorm(const int32_t* rows, const float* ln_w, const float* ln_b, float eps, void* ln_out, float* ln_mean,
                                             float* ln_rstd) {
   GT_CHECK_ARG(rows && ln_w && ln_b && ln_out && ln_mean && ln_rstd, "null buffer");
-  g_pending.map = LinRowMap{rows, ln_w, ln_b, ln_out, ln_mean, ln_rstd, eps};
+  LinRowMap& p = g_pending.map;   // (a pending gt_linear_set_rows_add stays)
+  p.rows = rows; p.ln_w = ln_w; p.ln_b = ln_b; p.ln_out = ln_out; p.ln_mean = ln_mean; p.ln_rstd = ln_rstd; p.ln_eps = eps;
+  return GT_OK;
+}
+// ... and a row-gathered fp32 addend for the next forward GEMM with a row map (gt_linear_set_rows / _layernorm, in either order): the
+// stored row of GEMM row m is T(row m + table[idx[m]][0..N)), the sum in fp32 behind bias / activation and before the LayerNorm;
+// idx[m] < 0 adds nothing.  table: fp32, 16-byte aligned, pitch ld >= N, ld % 4 == 0; idx: int32 [M] (gt_seq_positions).  Taken and
+// cleared by the next public forward or backward call like the row map; a call without a row map, and every backward, refuses it.
+extern "C" int gt_linear_set_rows_add(const float* table, const int32_t* idx, int64_t ld) {
+  GT_CHECK_ARG(table && idx && ld > 0, "null buffer");
+  g_pending.map.add_table = table; g_pending.map.add_idx = idx; g_pending.map.add_ld = ld;
   return GT_OK;
 }
 // Y[M][N] = [X1 | X2] W^T + b with X1 [M][K1] (pitch ldx1), X2 [M][K2] (pitch ldx2), W [N][K1 + K2]; fp32 rows, y_dtype fp32 / bf16

@@ -68,8 +68,13 @@ struct L32Args {
   void* ln_out;              // [.][ldo], TO
   float *ln_mean, *ln_rstd;
   float ln_eps;
+  // k_lin3 forward only, with out_rows, not the GELU instantiations -- a ROW-GATHERED addend (PositionalEncoding on the token rows,
+  // models/gnn_transformer.py:149-168): out row m += add_tab[add_idx[m]][0..Nout) (fp32, pitch add_ld; add_idx[m] < 0: nothing), in
+  // fp32 after bias / activation / dropout / add1 / add2 and before the LayerNorm above and the store
+  const float* add_tab;
+  const int32_t* add_idx;
+  int64_t add_ld;
   // host side only (the launchers of linear3x.h / linear3r.h): the call allows "high", three bf16 products per fp32 product
-  // (sits in the struct's tail padding: the kernels' argument layout is what it was)
   int high;
 };
 

@@ -406,6 +406,15 @@ __global__ void __launch_bounds__(256, 2) k_lin3(L32Args a) {
       }
     }
     if constexpr (!GELU) {   // (the gelu instantiations have no registers left for it, and no caller)
+    if (a.add_tab) {   // + add_tab[add_idx[row]] (L32Args::add_tab: the positional-encoding row of a node's token row), fp32
+#pragma unroll
+      for (int t = 0; t < HT; ++t) {
+        if (!ok[t]) continue;
+        const int c = lane + t * 64;
+        const int32_t q = a.add_idx[mrow0 + c / CPR];
+        if (q >= 0) v[t] = gt_add4(v[t], *reinterpret_cast<const float4*>(a.add_tab + (int64_t)q * a.add_ld + ncol0 + (c % CPR) * 4));
+      }
+    }
     if (a.ln_out) {
       // ---- LayerNorm of the row in the same epilogue (Nout = NT x 16: the block holds whole rows, half in each column wave):
       // two-pass statistics like k_ln_fwd on the STORED values (TO rounding first), the halves meet through LDS.  Every lane's HT
@@ -511,7 +520,7 @@ static inline int w3_pick_mt(int64_t M, int ncb) {
 // "high" (L32Args::high) runs three products in k_lin3: fp32 rows in and out with bias / ReLU / gate / addends (grouped or not, a
 // virtual concatenation included); the GELU, row-map and LayerNorm-epilogue forms and bf16 rows on either side keep six
 static inline bool w3_high(int ta, int to, const L32Args& a) {
-  return a.high && ta == GT_F32 && to == GT_F32 && a.act != 2 && !a.gout && !a.a_rows && !a.out_rows && !a.ln_out;
+  return a.high && ta == GT_F32 && to == GT_F32 && a.act != 2 && !a.gout && !a.a_rows && !a.out_rows && !a.ln_out && !a.add_tab;
 }
 
 template <bool MASK>

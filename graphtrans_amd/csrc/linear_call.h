@@ -11,11 +11,16 @@
 
 // forward: output row m is stored at row rows[m] of y; backward: row m of dY is row rows[m] of dy; -1 = no such row (gt_linear_set_rows)
 // forward only: + a LayerNorm of the stored output row in the same epilogue when ln_out is set (gt_linear_set_rows_layernorm)
+// forward only: + a row-gathered fp32 addend, y[rows[m]] = T(gemm row m + add_table[add_idx[m]][0..N)) with the sum in fp32 (before the
+// LayerNorm above; add_idx[m] < 0: nothing added) when add_table is set (gt_linear_set_rows_add); needs `rows`
 struct LinRowMap {
   const int32_t* rows;
   const float *ln_w, *ln_b;
   void* ln_out;
   float *ln_mean, *ln_rstd, ln_eps;
+  const float* add_table;
+  const int32_t* add_idx;
+  int64_t add_ld;
 };
 struct LinFwd {
   int x_dtype, y_dtype, compute;

@@ -55,6 +55,8 @@ struct Ctx {
   // forward arena
   size_t o_rowmap;   // int32 [N]: the token row of every node (gt_seq_token_rows), when gnn2transformer writes the token rows itself
   int fuse_rows;
+  size_t o_pos;      // int32 [N]: the padded position of every node (gt_seq_positions), when the model has a positional encoding (gt_model::pe)
+  int64_t S_host;    // min(max nodes per graph, max_input_len) where the host knows it (else read on the device: meta[3] of the layout)
   size_t o_h[MAXL + 1], o_x0, o_vn[MAXL], o_vn_saved[MAXL], o_conv_saved[MAXL], o_cat, o_hn, o_tok, o_xin, o_st0, o_xe[MAXL],
       o_enc_saved[MAXL], o_hgin, o_sto, o_eplan, o_esort_ws, o_ne_x, o_ne_w, o_hg, o_ws, o_ws2, o_wt[MAXL], o_g2t_wt;
   size_t o_scales, q_dimg;
@@ -99,6 +101,11 @@ int model_check(const char* fn, const gt_model* m) {
   if (!m->conv_layers || (m->n_enc && !m->enc) || (m->has_vn && m->L > 1 && !m->vn)) { gt_set_error("%s: null descriptor array", fn); return GT_ERR_INVALID_ARG; }
   if (m->D <= 0 || m->D % 4 || m->d <= 0 || m->d % 8) { gt_set_error("%s: bad widths", fn); return GT_ERR_INVALID_ARG; }
   if (m->conv != GT_CONV_GCN && m->conv != GT_CONV_GIN && m->conv != GT_CONV_PNA) { gt_set_error("%s: bad conv kind", fn); return GT_ERR_INVALID_ARG; }
+  // every position is < S <= max_input_len: a table of at least that many rows needs no clamp in the kernels
+  if (m->pe && (m->pe_rows < m->max_input_len || ((uintptr_t)m->pe & 15))) {
+    gt_set_error("%s: the positional-encoding table needs max_input_len rows and 16-byte alignment", fn);
+    return GT_ERR_INVALID_ARG;
+  }
   if (m->conv == GT_CONV_PNA && (m->has_vn || m->jk_cat || !m->residual || !m->pna_src || !m->pna_img || !m->pna_map || !m->pna_inv)) {
     gt_set_error("%s: the PNA stack runs without a virtual node, with JK = last, the residual connection and its weight images", fn);
     return GT_ERR_INVALID_ARG;
@@ -112,12 +119,14 @@ int model_check(const char* fn, const gt_model* m) {
 struct HostLayout {
   int64_t rows, max_npos, num_work;
   size_t o_last, o_work, bytes;
+  int64_t S;
 };
 HostLayout layout_sizes(const int64_t* n, int64_t B, int64_t max_input_len, int cls, std::vector<int64_t>* kvlen_out) {
   int64_t S = 0;
   for (int64_t b = 0; b < B; ++b) S = std::max(S, n[b]);
   S = std::min(S, max_input_len);
   HostLayout h{};
+  h.S = S;
   int64_t cnt[8] = {0, 0, 0, 0, 0, 0, 0, 0};
   std::vector<int64_t>& kv = *kvlen_out;
   kv.resize((size_t)B);
@@ -239,11 +248,14 @@ extern "C" int gt_model_prepare(const gt_model* m, const gt_model_batch* b, void
   c->use_prep = (m->st_prep && b->sizes_host && c->build_graph && E >= PREP_MIN_EDGES) ? 1 : 0;
   if (b->seq_desc) {
     c->rows = b->rows; c->max_npos = b->max_npos; c->num_work = b->num_work; c->exact = b->lay_exact;
+    c->S_host = b->lay_S;
+    GT_CHECK_ARG(!m->pe || b->lay_meta || b->lay_S > 0, "a caller's token layout needs its S (lay_S or lay_meta) for the positional encoding");
   } else if (b->sizes_host) {
     std::vector<int64_t> kv;
     const HostLayout h = layout_sizes(b->sizes_host, B, m->max_input_len, cls, &kv);
     c->rows = h.rows; c->max_npos = h.max_npos; c->num_work = h.num_work; c->exact = 1;
     c->lay_host = 1;
+    c->S_host = h.S;
     c->lay_bytes = h.bytes; c->lay_o_last = h.o_last; c->lay_o_work = h.o_work;
     gt_stage_ring* ring = b->ring;
     GT_CHECK_ARG(ring && ring->base && ring->slots > 0 && ring->slots <= 64, "host-built layout needs a staging ring");
@@ -343,8 +355,9 @@ extern "C" int gt_model_prepare(const gt_model* m, const gt_model_batch* b, void
     c->cat2 = gt_linear_cat2_ok(c->compute, m->g2t_w, N, d, D, D) ? 1 : 0;
   }
   c->o_cat = a.take((m->jk_cat && !c->cat2) ? (size_t)N * Kc * 4 : 0);
-  c->o_hn = a.take((size_t)N * d * tsz);
+  c->o_hn = a.take((size_t)N * d * (m->pe ? 4 : tsz));   // (fp32 under a positional encoding: its add comes before the one rounding)
   c->o_rowmap = a.take((size_t)N * 4);
+  c->o_pos = a.take(m->pe ? (size_t)N * 4 : 0);
   c->o_tok = a.take((size_t)rows * d * tsz);
   if (m->nin_w) {
     c->o_xin = a.take((size_t)rows * d * tsz);
@@ -726,6 +739,15 @@ extern "C" int gt_model_forward(const gt_model* m, void* ctx_, void* arena, floa
   // ... and norm_input (transformer_encoder.py:53-57) in the same epilogue when a token row fills one column block of the kernel
   const bool fuse_nin = c->fuse_rows && m->nin_w && gt_linear_rows_layernorm_ok(d);
   LinRowMap map{};   // rides, like the second operand below, in the GEMM call's record
+  // PositionalEncoding (models/gnn_transformer.py:98-100, :149-168: x + pe[:S] on the padded rows, before CLS and norm_input): the
+  // row pe[padded position of the node] joins the node's token row where that row is written -- the GEMM's epilogue or the gather
+  const int32_t* pos = nullptr;
+  if (m->pe) {
+    const int32_t* S_dev = c->build_layout_dev ? (const int32_t*)P(c->o_lay_meta) + 3 : ((b.seq_desc && b.lay_meta) ? b.lay_meta + 3 : nullptr);
+    GT_TRY(gt_seq_positions(graph_ptr, node_graph, c->seq_desc, m->with_cls ? 1 : 0, N, c->S_host, S_dev, (int32_t*)P(c->o_pos), st));
+    pos = (const int32_t*)P(c->o_pos);
+  }
+  const int g2t_dt = (m->pe && !c->fuse_rows) ? GT_F32 : tdt;   // (the gather adds in fp32 and rounds once)
   if (c->fuse_rows) {
     int32_t* rmap = (int32_t*)P(c->o_rowmap);
     if (fuse_nin) {
@@ -737,12 +759,13 @@ extern "C" int gt_model_forward(const gt_model* m, void* ctx_, void* arena, floa
       GT_TRY(gt_seq_token_rows(tdt, m->cls, graph_ptr, node_graph, c->seq_desc, B, 1, m->with_cls ? 1 : 0, N, d, P(c->o_tok), rmap, st));
       map.rows = rmap;
     }
+    if (m->pe) { map.add_table = m->pe; map.add_idx = pos; map.add_ld = d; }
     g2t_out = P(c->o_tok);
   }
   LinFwd g2t{};
   if (c->cat2) {
     c->node_rep = nullptr;
-    g2t = LinFwd{GT_F32, tdt, compute, c->first, m->g2t_w, m->g2t_b, g2t_out, N, d, 2 * D, D, d, 1, 0, 0, 0, 0.f, 0, (hipStream_t)st};
+    g2t = LinFwd{GT_F32, g2t_dt, compute, c->first, m->g2t_w, m->g2t_b, g2t_out, N, d, 2 * D, D, d, 1, 0, 0, 0, 0.f, 0, (hipStream_t)st};
     g2t.x2 = c->h_last; g2t.x_split = D; g2t.ldx2 = D;
   } else {
     if (m->jk_cat) {   // torch.cat([h_list[0], h_list[-1]], 1)   (gnn_module.py:104-105)
@@ -752,12 +775,17 @@ extern "C" int gt_model_forward(const gt_model* m, void* ctx_, void* arena, floa
     } else {
       c->node_rep = c->h_last;
     }
-    g2t = LinFwd{GT_F32, tdt, compute, c->node_rep, m->g2t_w, m->g2t_b, g2t_out, N, d, c->Kc, c->Kc, d, 1, 0, 0, 0, 0.f, 0, (hipStream_t)st};
+    g2t = LinFwd{GT_F32, g2t_dt, compute, c->node_rep, m->g2t_w, m->g2t_b, g2t_out, N, d, c->Kc, c->Kc, d, 1, 0, 0, 0, 0.f, 0, (hipStream_t)st};
   }
   g2t.map = map;
   GT_TRY(lin_fwd(g2t));
-  if (!c->fuse_rows)
-    GT_TRY(gt_seq_gather_cls32(tdt, P(c->o_hn), m->cls, graph_ptr, c->seq_desc, B, 1, c->max_npos, m->with_cls ? 1 : 0, d, P(c->o_tok), st));
+  if (!c->fuse_rows) {
+    if (m->pe)
+      GT_TRY(gt_seq_gather_add(tdt, GT_F32, P(c->o_hn), nullptr, m->cls, m->pe, d, pos, graph_ptr, c->seq_desc, B, 1, c->max_npos, m->with_cls ? 1 : 0, d,
+                               P(c->o_tok), nullptr, st));
+    else
+      GT_TRY(gt_seq_gather_cls32(tdt, P(c->o_hn), m->cls, graph_ptr, c->seq_desc, B, 1, c->max_npos, m->with_cls ? 1 : 0, d, P(c->o_tok), st));
+  }
   const void* cur = P(c->o_tok);
   if (fuse_nin) {
     cur = P(c->o_xin);

@@ -153,14 +153,18 @@ __global__ void __launch_bounds__(SS_T) k_segsum_fixup(const T* __restrict__ add
 }
 
 // tokens[row(b,p)] <- node row | cls | 0 ; grid (position tiles, B)
-template <typename T>
-__global__ void __launch_bounds__(SEG_THREADS) k_seq_gather(const T* __restrict__ h, const T* __restrict__ cls,
+// With `table` (gt_seq_gather_add): node rows are TH (fp32 or the token type) and every node token row gets + table[pos[node]][0..D)
+// in fp32 before its ONE rounding to T (PositionalEncoding, models/gnn_transformer.py:149-168: x + pe[:S] on the padded layout);
+// CLS and pad rows are what they were.
+template <typename T, typename TH = T>
+__global__ void __launch_bounds__(SEG_THREADS) k_seq_gather(const TH* __restrict__ h, const T* __restrict__ cls,
                                                             const float* __restrict__ cls32,
                                                             const int32_t* __restrict__ gptr,
                                                             const int32_t* __restrict__ desc, int64_t row_stride,
                                                             int64_t max_npos, int with_cls, int64_t D,
                                                             T* __restrict__ tokens, uint8_t* __restrict__ pad_mask,
-                                                            int pos_per_block) {
+                                                            int pos_per_block, const float* __restrict__ table = nullptr,
+                                                            const int32_t* __restrict__ pos = nullptr, int64_t ldt = 0) {
   const int b = blockIdx.y;
   const int row0 = desc[b * 4 + 0], npos = desc[b * 4 + 1], kv_off = desc[b * 4 + 2], kv_len = desc[b * 4 + 3];
   const int kept = kv_len - with_cls;
@@ -175,8 +179,13 @@ __global__ void __launch_bounds__(SEG_THREADS) k_seq_gather(const T* __restrict_
     int64_t c = (i % C) * 4;
     int j = p - kv_off;
     float4 v = gt_zero4();
-    if (j >= 0 && j < kept) v = gt_load4<T>(h + (int64_t)(node0 + j) * D + c);
-    else if (with_cls && j == kept) v = cls32 ? gt_load4<float>(cls32 + c) : gt_load4<T>(cls + c);
+    if (j >= 0 && j < kept) {
+      v = gt_load4<TH>(h + (int64_t)(node0 + j) * D + c);
+      if (table) {
+        const int32_t q = pos[node0 + j];
+        if (q >= 0) v = gt_add4(v, gt_load4<float>(table + (int64_t)q * ldt + c));
+      }
+    } else if (with_cls && j == kept) v = cls32 ? gt_load4<float>(cls32 + c) : gt_load4<T>(cls + c);
     gt_store4<T>(tokens + ((int64_t)row0 + (int64_t)p * row_stride) * D + c, v);
   }
   if (pad_mask)
@@ -308,6 +317,63 @@ extern "C" int gt_seq_gather_cls32(int dtype, const void* h, const float* cls32,
                                    int with_cls, int64_t D, void* tokens, gt_stream_t stream_) {
   return seq_gather_impl("gt_seq_gather_cls32", dtype, h, nullptr, cls32, graph_ptr, seq_desc, num_seqs, row_stride, max_npos,
                          with_cls, D, tokens, nullptr, stream_);
+}
+
+// gt_seq_gather / gt_seq_gather_cls32 with a row-gathered fp32 addend: node rows h [N][D] of h_dtype (fp32, or the token type), token
+// rows of dtype; tokens[row of node r] = T(h[r] + table[pos[r]]) -- the sum in fp32, one rounding.  cls (token type) or cls32.
+extern "C" int gt_seq_gather_add(int dtype, int h_dtype, const void* h, const void* cls, const float* cls32, const float* table,
+                                 int64_t table_ld, const int32_t* pos, const int32_t* graph_ptr, const int32_t* seq_desc, int64_t num_seqs,
+                                 int64_t row_stride, int64_t max_npos, int with_cls, int64_t D, void* tokens, uint8_t* pad_mask,
+                                 gt_stream_t stream_) {
+  int rc = check("gt_seq_gather_add", dtype, D);
+  if (rc) return rc;
+  GT_CHECK_ARG(h_dtype == dtype || h_dtype == GT_F32, "node rows must be fp32 or of the token type");
+  GT_CHECK_ARG(h && graph_ptr && seq_desc && tokens && table && pos, "null buffer");
+  GT_CHECK_ARG(table_ld >= D && table_ld % 4 == 0, "the table's pitch must be >= dim and a multiple of 4");
+  GT_CHECK_ARG(!with_cls || cls || cls32, "with_cls needs the cls row");
+  if (num_seqs == 0 || max_npos == 0) return GT_OK;
+  GT_CHECK_ARG(num_seqs <= 65535, "more than 65535 sequences");
+  hipStream_t stream = (hipStream_t)stream_;
+  int ppb = rows_per_block(D, h_dtype == GT_F32 ? 4 : 2);
+  dim3 grid((unsigned)gt_cdiv(max_npos, ppb), (unsigned)num_seqs);
+  if (dtype == GT_F32)
+    hipLaunchKernelGGL((k_seq_gather<float, float>), grid, dim3(SEG_THREADS), 0, stream, (const float*)h, (const float*)cls, cls32, graph_ptr,
+                       seq_desc, row_stride, max_npos, with_cls, D, (float*)tokens, pad_mask, ppb, table, pos, table_ld);
+  else if (h_dtype == GT_F32)
+    hipLaunchKernelGGL((k_seq_gather<gt_bf16, float>), grid, dim3(SEG_THREADS), 0, stream, (const float*)h, (const gt_bf16*)cls, cls32,
+                       graph_ptr, seq_desc, row_stride, max_npos, with_cls, D, (gt_bf16*)tokens, pad_mask, ppb, table, pos, table_ld);
+  else
+    hipLaunchKernelGGL((k_seq_gather<gt_bf16, gt_bf16>), grid, dim3(SEG_THREADS), 0, stream, (const gt_bf16*)h, (const gt_bf16*)cls, cls32,
+                       graph_ptr, seq_desc, row_stride, max_npos, with_cls, D, (gt_bf16*)tokens, pad_mask, ppb, table, pos, table_ld);
+  GT_CHECK_LAUNCH();
+  return GT_OK;
+}
+
+// The PADDED position of every node (beside k_seq_token_rows): pad_batch left-pads to S = min(max nodes per graph, max_input_len)
+// (modules/utils.py:16-25), so the j-th kept node of graph b -- node row graph_ptr[b+1] - kept_b + j -- sits at position
+// S - kept_b + j, whatever the token layout; -1 for the leading nodes a truncated graph drops.  S: *S_dev when given (meta[3] of
+// gt_seq_layout_packed: no device->host copy), else the host value.
+__global__ void __launch_bounds__(SEG_THREADS) k_seq_positions(const int32_t* __restrict__ gptr, const int32_t* __restrict__ node_graph,
+                                                               const int32_t* __restrict__ desc, int with_cls, int64_t N, int S_host,
+                                                               const int32_t* __restrict__ S_dev, int32_t* __restrict__ pos) {
+  const int S = S_dev ? *S_dev : S_host;
+  for (int64_t r = (int64_t)blockIdx.x * SEG_THREADS + threadIdx.x; r < N; r += (int64_t)gridDim.x * SEG_THREADS) {
+    const int b = node_graph[r];
+    const int kept = desc[b * 4 + 3] - with_cls;
+    const int node0 = gptr[b + 1] - kept;
+    pos[r] = r >= node0 ? S - kept + ((int)r - node0) : -1;
+  }
+}
+extern "C" int gt_seq_positions(const int32_t* graph_ptr, const int32_t* node_graph, const int32_t* seq_desc, int with_cls, int64_t N,
+                                int64_t S, const int32_t* S_dev, int32_t* pos, gt_stream_t stream_) {
+  GT_CHECK_ARG(graph_ptr && node_graph && seq_desc && pos, "null buffer");
+  GT_CHECK_ARG(N >= 0 && N <= 0x7fffffff && (S_dev || (S >= 0 && S <= 0x7fffffff)), "bad sizes");
+  if (N == 0) return GT_OK;
+  const int64_t g = gt_cdiv(N, SEG_THREADS);
+  hipLaunchKernelGGL(k_seq_positions, dim3((unsigned)(g < 1024 ? g : 1024)), dim3(SEG_THREADS), 0, (hipStream_t)stream_, graph_ptr, node_graph,
+                     seq_desc, with_cls ? 1 : 0, N, (int)S, S_dev, pos);
+  GT_CHECK_LAUNCH();
+  return GT_OK;
 }
 
 // out[c] = sum over rows of x[r][c], fp32, fixed order: (256 / CW) row groups x CW column chunks per block pass, CW = 16 / 32 / 64 by

@@ -74,7 +74,7 @@ class ModelDesc(C.Structure):   # gt_model
                 ("ev_prep_begin", _vp), ("ev_graph", _vp), ("ev_w1", _vp), ("w3", ImageSet), ("w3_enc", ImageSet), ("w1", ImageSet),
                 ("pna_src", _vp), ("pna_img", _vp), ("pna_map", _vp), ("pna_inv", _vp), ("pna_n_img", _i64), ("pna_n_src", _i64),
                 ("off_pna_src", _i64), ("pna_img_off", (_i64 * 4) * MAXL), ("pna_kinds", _i32 * 8), ("pna_avg_log", _f32),
-                ("pna_avg_lin", _f32)]
+                ("pna_avg_lin", _f32), ("pe", _vp), ("pe_rows", _i64)]
 
 
 class BatchDesc(C.Structure):   # gt_model_batch
@@ -85,7 +85,8 @@ class BatchDesc(C.Structure):   # gt_model_batch
                 ("x", _vp), ("x_stride0", _i64), ("x_stride1", _i64), ("node_depth", _vp), ("depth_stride", _i64), ("edge_attr", _vp),
                 ("zeros_B", _vp), ("ident_B", _vp), ("ptr01", _vp)] + \
                [(k, _i32) for k in ("training", "compute", "tdt", "will_bwd", "use_w3", "use_w1", "sync_bn", "pad2_")] + \
-               [("gnn_p", _f32), ("enc_p", _f32), ("gnn_seed", C.c_uint64), ("enc_seed", C.c_uint64), ("ring", _vp)]
+               [("gnn_p", _f32), ("enc_p", _f32), ("gnn_seed", C.c_uint64), ("enc_seed", C.c_uint64), ("ring", _vp),
+                ("lay_S", _i64), ("lay_meta", _vp)]
 
 
 class SizesDesc(C.Structure):   # gt_model_sizes
@@ -320,6 +321,12 @@ class _Plan:
         cm.D, cm.d, cm.Nh, cm.ldy = D, d, self.Nh, self.ldy
         cm.max_input_len = int(enc.max_input_len)
         cm.with_cls = int(self.cls is not None)
+        # PositionalEncoding (token_layout="packed" only, see GNNTransformer._use_packed): the module's buffer, read as [max_len][d]
+        pe = getattr(model, "pos_encoder", None)
+        self.pe = pe.pe if pe is not None else None
+        self.pe_ptr = self.pe.data_ptr() if pe is not None else 0
+        if pe is not None:
+            cm.pe, cm.pe_rows = self.pe_ptr, int(self.pe.shape[0])
         cm.vn_defer_dw = int(VN_DEFER_DW)
         cm.conv_layers = C.cast(self.conv_desc, _vp)
         cm.vn = C.cast(self.vn_desc, _vp) if nvn else None
@@ -658,7 +665,8 @@ def _bn_sync_hook(model, plan):
 def _plan(model):
     st = state(model)
     plan = st.get("plan")
-    if plan is None or plan.param_ptrs != tuple(p.data_ptr() for p in plan.plist):
+    pe = getattr(model, "pos_encoder", None)   # (a buffer moves with .to() like the parameters)
+    if plan is None or plan.param_ptrs != tuple(p.data_ptr() for p in plan.plist) or plan.pe_ptr != (pe.pe.data_ptr() if pe is not None else 0):
         plan = st["plan"] = _Plan(model)
     return plan
 
@@ -693,6 +701,9 @@ def eligible(model, batched_data, perturb):
         ok = cache[key] = _eligible_static(model)
     if not ok:
         return False
+    pos = getattr(model, "pos_encoder", None)
+    if pos is not None and not (pos.dropout.p == 0 and pos.pe.is_cuda and pos.pe.dtype == torch.float32 and pos.pe.is_contiguous()):
+        return False   # (changed since the static answer was cached: the module path raises GNNTransformer._packed_pe's message)
     x = batched_data.x
     gnn = model.gnn_node
     ne = gnn.node_encoder
@@ -949,6 +960,10 @@ class _FusedModel(torch.autograd.Function):
                 work = getattr(lay, "work", None)
                 bt.work_items = work.data_ptr() if work is not None else None
                 bt.rows, bt.max_npos, bt.num_work, bt.lay_exact = lay.rows, lay.max_npos, getattr(lay, "num_work", 0), int(lay.exact)
+                if lay.exact:   # S for the positional encoding: a host value, or meta[3] of the device-built layout
+                    bt.lay_S = int(lay.S)
+                else:
+                    bt.lay_meta = lay.meta.data_ptr()
                 keep.append(lay)
         else:
             ei = batched_data.edge_index

@@ -195,6 +195,7 @@ class SeqLayout:
             raise ValueError(kind)
         self.kind, self.with_cls, self.S, self.B = kind, with_cls, S, B
         self.kept = kept
+        self._n = n
         self.desc_cpu = desc
         # attention tile list: (sequence, 64-position tile) for every tile that exists (ragged sizes)
         # Longest sequences FIRST: a block walks all keys (queries) of its sequence tile by tile, so the longest sequence's
@@ -255,3 +256,12 @@ class SeqLayout:
             self.work = torch.from_numpy(work)
             self.desc = torch.from_numpy(desc)
             self.last_rows = torch.from_numpy(last_row)
+
+    def positions(self):
+        """int32 [N] (host, exact layouts): the padded position of every node -- pad_batch left-pads to S (modules/utils.py:16-25),
+        so the j-th kept node of graph b, node row graph_ptr[b+1] - kept_b + j, sits at S - kept_b + j; -1 for the nodes a truncated
+        graph drops.  What PositionalEncoding indexes its table by, whatever the token layout (csrc/segment.hip:k_seq_positions)."""
+        n, kept, S = np.asarray(self._n, dtype=np.int64), np.asarray(self.kept, dtype=np.int64), self.S
+        j = np.arange(int(n.sum()), dtype=np.int64) - np.repeat(np.cumsum(n) - n, n)   # index of the node inside its graph
+        drop = np.repeat(n - kept, n)
+        return np.where(j >= drop, S - np.repeat(kept, n) + (j - drop), -1).astype(np.int32)

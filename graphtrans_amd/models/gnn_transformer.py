@@ -8,6 +8,8 @@ forward() picks between two equivalent data paths:
              on): node rows -> token rows with NO padding rows at all; every Linear/LayerNorm/FFN
              and the attention kernel touch only real tokens.  Outputs equal the padded path's
              (padding never influences valid rows: masked keys, per-token FFN/LN).
+             With pos_encoder only on request (token_layout="packed"): a token row gets the table
+             row of the position pad_batch would have put it at (graph.SeqLayout.positions).
   * padded  (the reference layout (S,B,d), exact for `mean` pooling which sums padded rows,
              gnn_transformer.py:117): pad_batch -> [pos_encoder] -> [masked encoder] -> encoder.
 """
@@ -36,6 +38,8 @@ class GNNTransformer(BaseModel):
         MaskedOnlyTransformerEncoder.add_args(parser)
         group = parser.add_argument_group("GNNTransformer - Training Config")
         group.add_argument("--pos_encoder", default=False, action="store_true")
+        group.add_argument("--token_layout", type=str, default="auto", choices=["auto", "packed", "padded"],
+                           help="token rows of the Transformer: packed (no pad rows), padded (the reference layout), auto")
         group.add_argument("--pretrained_gnn", type=str, default=None, help="pretrained gnn_node node embedding path")
         group.add_argument("--freeze_gnn", type=int, default=None, help="Freeze gnn_node weight from epoch `freeze_gnn`")
 
@@ -92,11 +96,32 @@ class GNNTransformer(BaseModel):
     def _use_packed(self):
         if self.layout == "padded":
             return False
-        ok = (self.pooling in ("cls", "last") and self.pos_encoder is None and self.num_encoder_layers_masked == 0
-              and self.num_encoder_layers > 0)
-        if self.layout == "packed" and not ok:
-            raise ValueError("token_layout='packed' needs cls/last pooling, no pos_encoder, no masked encoder")
-        return ok
+        ok = self.pooling in ("cls", "last") and self.num_encoder_layers_masked == 0 and self.num_encoder_layers > 0
+        if self.layout != "packed":   # "auto": a positional encoding keeps the padded layout
+            return ok and self.pos_encoder is None
+        if not ok:
+            raise ValueError("token_layout='packed' needs cls/last pooling and no masked encoder "
+                             "(mean pooling and the masked encoder run on the padded layout only)")
+        if self.pos_encoder is not None:
+            self._packed_pe()
+        return True
+
+    def _packed_pe(self):
+        """The `pe` table as the packed layout's kernels read it ([max_len][d_model] fp32 rows); ValueError when they cannot."""
+        pos, enc = self.pos_encoder, self.transformer_encoder
+        pe = pos.pe
+        why = None
+        if pos.dropout.p != 0:
+            why = "pos_encoder.dropout.p == 0"
+        elif not (pe.dtype == torch.float32 and pe.is_contiguous() and pe.device == self.gnn2transformer.weight.device):
+            why = "a contiguous fp32 pos_encoder.pe buffer on the model's device"
+        elif not (pe.dim() == 3 and pe.shape[1] == 1 and pe.shape[2] == enc.d_model):
+            why = "pos_encoder.pe of shape (max_len, 1, d_model)"
+        elif int(enc.max_input_len) > pe.shape[0]:
+            why = "max_input_len <= pos_encoder.pe.shape[0] (every padded position needs a table row)"
+        if why is not None:
+            raise ValueError("token_layout='packed' with pos_encoder needs " + why)
+        return pe
 
     def forward(self, batched_data, perturb=None):
         if batched_data.batch.numel() == 0:
@@ -117,7 +142,8 @@ class GNNTransformer(BaseModel):
         if self._use_packed():
             with_cls = enc.cls_embedding is not None
             lay = gs.layout("packed", max_len, with_cls)
-            tokens, _ = ops.seq_gather(h_node, enc.cls_embedding if with_cls else None, gs, lay)
+            pe = self._packed_pe() if self.pos_encoder is not None else None
+            tokens, _ = ops.seq_gather(h_node, enc.cls_embedding if with_cls else None, gs, lay, pe=pe)
             h_graph = enc.forward_tokens(tokens, lay, pooled=True).float()  # out[-1] of every sequence (the only rows read)
         else:
             padded_h_node, src_padding_mask, num_nodes, mask, max_num_nodes = pad_batch(

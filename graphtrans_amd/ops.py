@@ -217,10 +217,29 @@ def segment_sum(x, gs, add=None):
 # ------------------------------------------------------------------------------------------------
 # node rows <-> token rows
 # ------------------------------------------------------------------------------------------------
-def _gather_raw(h, cls, gs, lay, want_mask):
+def seq_positions(gs, lay):
+    """int32 [N]: the padded position of every node (gt_seq_positions; -1 = dropped by truncation), cached on the layout"""
+    pos = getattr(lay, "_pos", None)
+    if pos is None:
+        pos = torch.empty(max(gs.N, 1), dtype=torch.int32, device=gs.graph_ptr.device)
+        meta = getattr(lay, "meta", None)   # device-built layout: S is meta[3], read on the device
+        _lib.launch("gt_seq_positions", _ptr(gs.graph_ptr), _ptr(gs.node_graph), _ptr(lay.desc), 1 if lay.with_cls else 0, gs.N,
+                    0 if meta is not None else int(lay.S), (meta.data_ptr() + 12) if meta is not None else None, _ptr(pos), _stream())
+        lay._pos = pos
+    return pos
+
+
+def _gather_raw(h, cls, gs, lay, want_mask, pe=None):
     D = h.shape[1]
     tokens = (torch.empty if getattr(lay, "exact", True) else torch.zeros)((lay.rows, D), dtype=h.dtype, device=h.device)
     mask = torch.empty((lay.B, lay.max_npos), dtype=torch.bool, device=h.device) if want_mask else None
+    if pe is not None:   # + pe[padded position] on every node token row (fp32 add, one rounding)
+        if not (pe.is_cuda and pe.dtype == torch.float32 and pe.is_contiguous() and pe.shape[-1] == D and pe.numel() == pe.shape[0] * D):
+            raise ValueError("seq_gather: pe must be a contiguous fp32 (max_len, [1,] D) table on the GPU")
+        pos = seq_positions(gs, lay)
+        _lib.launch("gt_seq_gather_add", _dtype_code(h), _dtype_code(h), _ptr(h), _ptr(cls), None, _ptr(pe), D, _ptr(pos), _ptr(gs.graph_ptr),
+                    _ptr(lay.desc), lay.B, lay.row_stride, lay.max_npos, 1 if lay.with_cls else 0, D, _ptr(tokens), _ptr(mask), _stream())
+        return tokens, mask
     _lib.launch("gt_seq_gather", _dtype_code(h), _ptr(h), _ptr(cls), _ptr(gs.graph_ptr), _ptr(lay.desc), lay.B,
                 lay.row_stride, lay.max_npos, 1 if lay.with_cls else 0, D, _ptr(tokens), _ptr(mask), _stream())
     return tokens, mask
@@ -238,11 +257,11 @@ def _scatter_raw(tokens, base, gs, lay, want_cls):
 
 class _SeqGather(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, h, cls, gs, lay, want_mask):
+    def forward(ctx, h, cls, gs, lay, want_mask, pe=None):
         ctx.set_materialize_grads(False)
         h = _dev(h, "h")
         cls_c = None if cls is None else _dev(cls.reshape(-1).to(h.dtype), "cls")
-        tokens, mask = _gather_raw(h, cls_c, gs, lay, want_mask)
+        tokens, mask = _gather_raw(h, cls_c, gs, lay, want_mask, pe)
         ctx.gs, ctx.lay = gs, lay
         ctx.cls_meta = None if cls is None else (cls.shape, cls.dtype)
         if mask is not None:
@@ -256,12 +275,14 @@ class _SeqGather(torch.autograd.Function):
         if dcls is not None:
             shape, dt = ctx.cls_meta
             dcls = dcls.float().sum(0).reshape(shape).to(dt)
-        return dh, dcls, None, None, None
+        return dh, dcls, None, None, None, None
 
 
-def seq_gather(h, cls, gs, lay, want_mask=False):
-    """tokens (lay.rows, d) [+ padding mask (B, max_npos), True = padding] from node rows."""
-    return _SeqGather.apply(h, cls, gs, lay, want_mask)
+def seq_gather(h, cls, gs, lay, want_mask=False, pe=None):
+    """tokens (lay.rows, d) [+ padding mask (B, max_npos), True = padding] from node rows.
+    pe: a PositionalEncoding table (max_len, [1,] d) fp32 -- every node token row gets + pe[its padded position] (a constant: the
+    backward is the plain scatter)."""
+    return _SeqGather.apply(h, cls, gs, lay, want_mask, pe)
 
 
 class _SeqScatter(torch.autograd.Function):

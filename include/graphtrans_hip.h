@@ -559,6 +559,12 @@ int gt_linear_set_rows(const int32_t* rows);
 int gt_linear_rows_layernorm_ok(int64_t N);
 int gt_linear_set_rows_layernorm(const int32_t* rows, const float* ln_w, const float* ln_b, float eps, void* ln_out, float* ln_mean,
                                  float* ln_rstd);
+/* ... with a row-gathered fp32 addend (forward only; PositionalEncoding on the token rows, models/gnn_transformer.py:149-168): the stored
+ * row of GEMM row m = T(row m + table[idx[m]][0..N)), the sum in fp32 behind bias / activation and before the LayerNorm above and the
+ * one rounding to y's type; idx[m] < 0 adds nothing.  table: fp32, 16-byte aligned, pitch ld >= N, ld % 4 == 0; idx: int32 [M] on the
+ * device (gt_seq_positions).  Composes with gt_linear_set_rows / gt_linear_set_rows_layernorm in either order and is consumed with
+ * them; a forward call without a row map, a GEMM that takes none, and every backward call refuse it (and clear it). */
+int gt_linear_set_rows_add(const float* table, const int32_t* idx, int64_t ld);
 int gt_linear_fwd_cat2(int y_dtype, int compute, const void* x1, int64_t K1, int64_t ldx1, const void* x2, int64_t K2, int64_t ldx2,
                        const float* weight, const float* bias, void* y, int64_t M, int64_t N, int64_t ldy, gt_stream_t stream);
 int gt_linear_bwd_cat2(int y_dtype, int compute, const void* x1, int64_t K1, int64_t ldx1, const void* x2, int64_t K2, int64_t ldx2,
@@ -978,6 +984,11 @@ typedef struct gt_model {
   int64_t pna_img_off[GT_MODEL_MAX_LAYERS][4];
   int32_t pna_kinds[8];          /* degree scalers of the S output blocks (gt_pna_scales) */
   float pna_avg_log, pna_avg_lin;
+  /* PositionalEncoding (models/gnn_transformer.py:149-168) or NULL: the module's `pe` buffer read as [pe_rows][d] fp32, 16-byte aligned,
+   * pe_rows >= max_input_len.  The token row of the node at padded position p (gt_seq_positions) gets + pe[p], in fp32, before its one
+   * rounding to the token type; CLS rows get nothing; no gradient. */
+  const float* pe;
+  int64_t pe_rows;
 } gt_model;
 
 typedef struct gt_model_batch {
@@ -1006,6 +1017,10 @@ typedef struct gt_model_batch {
   float gnn_p, enc_p;
   uint64_t gnn_seed, enc_seed;
   gt_stage_ring* ring;
+  /* with seq_desc and gt_model::pe: S = min(max nodes per graph, max_input_len) of the caller's layout, as a host value (lay_S > 0) or
+   * on the device (lay_meta = the meta[4] of gt_seq_layout_packed, S = lay_meta[3]) */
+  int64_t lay_S;
+  const int32_t* lay_meta;
 } gt_model_batch;
 
 typedef struct gt_model_sizes {
@@ -1034,6 +1049,19 @@ int gt_seq_layout_packed_host(const int64_t* sizes_host, int64_t B, int64_t max_
 int gt_seq_gather_cls32(int dtype, const void* h, const float* cls32, const int32_t* graph_ptr, const int32_t* seq_desc,
                         int64_t num_seqs, int64_t row_stride, int64_t max_npos, int with_cls, int64_t dim,
                         void* tokens, gt_stream_t stream);
+/* The PADDED position of every node (PositionalEncoding adds pe[p] at position p of pad_batch's left-padded layout, modules/utils.py:16-25
+ * + models/gnn_transformer.py:98-100): with S = min(max_b n_b, max_input_len) and kept_b = min(n_b, S) = seq_desc[b].kv_len - with_cls,
+ * pos[graph_ptr[b+1] - kept_b + j] = S - kept_b + j for j in [0, kept_b), -1 for the nodes a truncated graph drops; int32 [N], the same
+ * for every token layout.  S: *S_dev (device int32, e.g. meta + 3 of gt_seq_layout_packed: no device->host copy) when S_dev != NULL,
+ * else the host value. */
+int gt_seq_positions(const int32_t* graph_ptr, const int32_t* node_graph, const int32_t* seq_desc, int with_cls, int64_t N, int64_t S,
+                     const int32_t* S_dev, int32_t* pos, gt_stream_t stream);
+/* gt_seq_gather / gt_seq_gather_cls32 (cls in the token type, or cls32 in fp32; pad_mask may be NULL) with a row-gathered addend: the
+ * token row of node r = T(h[r] + table[pos[r]][0..dim)), the sum in fp32 and ONE rounding to the token type `dtype`.  h: [N][dim] of
+ * h_dtype = GT_F32 or dtype; table: fp32 rows of pitch table_ld (>= dim, % 4); pos: gt_seq_positions.  CLS and pad rows as without. */
+int gt_seq_gather_add(int dtype, int h_dtype, const void* h, const void* cls, const float* cls32, const float* table, int64_t table_ld,
+                      const int32_t* pos, const int32_t* graph_ptr, const int32_t* seq_desc, int64_t num_seqs, int64_t row_stride,
+                      int64_t max_npos, int with_cls, int64_t dim, void* tokens, uint8_t* pad_mask, gt_stream_t stream);
 /* out[c] (fp32) = sum_r x[r][c] in a fixed order (the CLS embedding's gradient from its per-graph rows) */
 int gt_colsum_f32(int dtype, const void* x, int64_t rows, int64_t dim, float* out, gt_stream_t stream);
 /* ... over the rows row_idx[0 .. rows) of x only (the CLS rows of the token matrix) */
