@@ -186,6 +186,8 @@ SIGNATURES = {
     "gt_rows_gather": (_i, [_i, _p, _p, _i64, _i64, _p, _p]),
     "gt_rows_scatter": (_i, [_i, _p, _p, _i64, _i64, _i64, _p, _p]),
     "gt_seq_layout_packed_host": (_i, [_p, _i64, _i64, _i, _p, _sz, _p]),
+    "gt_seq_layout_host": (_i, [_i, _p, _i64, _i64, _i, _p, _sz, _p]),
+    "gt_stage_ring_take": (_i, [_p, _sz, _p, _p]),
     "gt_pna_layer_saved_bytes": (_sz, [_p]),
     "gt_pna_layer_workspace_bytes": (_sz, [_p]),
     "gt_pna_layer_grad_elems": (_i64, [_p]),

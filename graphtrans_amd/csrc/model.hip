@@ -14,6 +14,7 @@
 
 #include "host_seq.h"
 #include "linear_call.h"
+#include "seq_layout_host.h"
 
 namespace {
 
@@ -45,7 +46,7 @@ struct Ctx {
   // staging slot of the host-built layout
   void* stage_ptr;
   void* stage_event;
-  size_t lay_bytes, lay_o_last, lay_o_work;
+  SeqBlob lay;   // the layout blob's offsets (host-built and device-built alike)
   // batch descriptors
   gt_gcn_layer gcn[MAXL];
   gt_gin_layer gin[MAXL];
@@ -113,70 +114,33 @@ int model_check(const char* fn, const gt_model* m) {
   return GT_OK;
 }
 
-// ---- the packed token layout on the host (graphtrans_amd/graph.py:SeqLayout; modules/utils.py:5-29 + transformer_encoder.py:50-55)
-// desc[b] = {row0, npos, kv_off, kv_len}; last_rows[b]; attention work list {sequence, 64-position tile}: sequences dealt to the
-// eight XCD slices by length rank (longest first inside each slice), slices padded with {-1, 0} to equal size.
-struct HostLayout {
-  int64_t rows, max_npos, num_work;
-  size_t o_last, o_work, bytes;
-  int64_t S;
-};
-HostLayout layout_sizes(const int64_t* n, int64_t B, int64_t max_input_len, int cls, std::vector<int64_t>* kvlen_out) {
-  int64_t S = 0;
-  for (int64_t b = 0; b < B; ++b) S = std::max(S, n[b]);
-  S = std::min(S, max_input_len);
-  HostLayout h{};
-  h.S = S;
-  int64_t cnt[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-  std::vector<int64_t>& kv = *kvlen_out;
-  kv.resize((size_t)B);
-  for (int64_t b = 0; b < B; ++b) {
-    kv[(size_t)b] = std::min(n[b], S) + cls;
-    h.rows += kv[(size_t)b];
-    h.max_npos = std::max(h.max_npos, kv[(size_t)b]);
+// ---- the token layout of one forward: the caller's, built on the host into a staging slot of the caller's ring (seq_layout_host.h), or
+// built on the device by gt_model_forward (only upper bounds are known here)
+int prepare_layout(const gt_model* m, const gt_model_batch* b, Ctx* c) {
+  const int64_t N = b->N, B = b->B;
+  const int cls = m->with_cls ? 1 : 0;
+  if (b->seq_desc) {
+    c->rows = b->rows; c->max_npos = b->max_npos; c->num_work = b->num_work; c->exact = b->lay_exact;
+    c->S_host = b->lay_S;
+    GT_CHECK_ARG(!m->pe || b->lay_meta || b->lay_S > 0, "a caller's token layout needs its S (lay_S or lay_meta) for the positional encoding");
+  } else if (b->sizes_host) {
+    const SeqHostLayout h = seq_layout_rank(GT_SEQ_PACKED, b->sizes_host, B, m->max_input_len, cls);
+    c->rows = h.rows; c->max_npos = h.max_npos; c->num_work = h.num_work; c->exact = 1;
+    c->lay_host = 1;
+    c->S_host = h.S;
+    c->lay = h.blob;
+    GT_CHECK_ARG(b->ring, "host-built layout needs a staging ring");
+    GT_TRY(gt_stage_ring_take(b->ring, h.blob.bytes, &c->stage_ptr, &c->stage_event));
+    seq_layout_fill(h, (char*)c->stage_ptr);
+  } else {   // sizes unknown on the host: gt_seq_layout_packed on the device, upper bounds here
+    c->build_layout_dev = 1;
+    c->rows = N + B * cls;
+    c->max_npos = std::min<int64_t>(m->max_input_len, N) + cls;
+    c->num_work = B + c->rows / 64;
+    c->exact = 0;
+    c->lay = seq_blob(B, std::max<int64_t>(c->num_work, 1));
   }
-  // tiles per eighth need the length ranks: computed by the builder below; here an exact count through the same ranking
-  std::vector<int32_t> order((size_t)B);
-  for (int64_t b = 0; b < B; ++b) order[(size_t)b] = (int32_t)b;
-  std::stable_sort(order.begin(), order.end(), [&](int32_t a, int32_t c) { return kv[(size_t)a] > kv[(size_t)c]; });
-  for (int64_t r = 0; r < B; ++r) cnt[r % 8] += (kv[(size_t)order[(size_t)r]] + 63) / 64;
-  int64_t wpx = 0;
-  for (int x = 0; x < 8; ++x) wpx = std::max(wpx, cnt[x]);
-  h.num_work = B ? 8 * wpx : 0;
-  const size_t nd = (size_t)B * 16, nl = (size_t)B * 8, nw = (size_t)h.num_work * 8;
-  h.o_last = (nd + 15) / 16 * 16;
-  h.o_work = (h.o_last + nl + 15) / 16 * 16;
-  h.bytes = std::max(h.o_work + nw, (size_t)16);
-  return h;
-}
-void layout_fill(const std::vector<int64_t>& kv, int64_t B, const HostLayout& h, char* dst) {
-  int32_t* desc = (int32_t*)dst;
-  int64_t* last = (int64_t*)(dst + h.o_last);
-  int32_t* work = (int32_t*)(dst + h.o_work);
-  int64_t row = 0;
-  for (int64_t b = 0; b < B; ++b) {
-    const int64_t k = kv[(size_t)b];
-    desc[b * 4 + 0] = (int32_t)row;
-    desc[b * 4 + 1] = (int32_t)k;
-    desc[b * 4 + 2] = 0;
-    desc[b * 4 + 3] = (int32_t)k;
-    last[b] = row + k - 1;
-    row += k;
-  }
-  if (!B) return;
-  std::vector<int32_t> order((size_t)B);
-  for (int64_t b = 0; b < B; ++b) order[(size_t)b] = (int32_t)b;
-  std::stable_sort(order.begin(), order.end(), [&](int32_t a, int32_t c) { return kv[(size_t)a] > kv[(size_t)c]; });
-  const int64_t wpx = h.num_work / 8;
-  for (int64_t i = 0; i < h.num_work; ++i) { work[2 * i] = -1; work[2 * i + 1] = 0; }
-  for (int x = 0; x < 8; ++x) {
-    int64_t pos = (int64_t)x * wpx;
-    for (int64_t r = x; r < B; r += 8) {
-      const int32_t s = order[(size_t)r];
-      const int64_t t = (kv[(size_t)s] + 63) / 64;
-      for (int64_t j = 0; j < t; ++j) { work[2 * pos] = s; work[2 * pos + 1] = (int32_t)j; ++pos; }
-    }
-  }
+  return GT_OK;
 }
 
 int bind_images(const gt_model* m, const Ctx* c) {
@@ -238,41 +202,14 @@ extern "C" int gt_model_prepare(const gt_model* m, const gt_model_batch* b, void
   c->tdt = b->tdt;
   c->tsz = gt_elt_bytes(b->tdt);
   const size_t tsz = c->tsz;
-  const int cls = m->with_cls ? 1 : 0;
 
-  // ---- token layout
+  // ---- graph structure and token layout: who builds them
   c->build_graph = b->graph_ptr == nullptr;
   // the prep stream pays for its stream switches and events (~0.4 ms of host time per step) only when the structure kernels are long:
   // measured r4, Code2 / Molpcba / PNA (E <= 1e5): same step time with and without, host 0.15-0.4 ms cheaper without; the
   // Erdos-Renyi stress (E = 1.05 M): 1 % faster with
   c->use_prep = (m->st_prep && b->sizes_host && c->build_graph && E >= PREP_MIN_EDGES) ? 1 : 0;
-  if (b->seq_desc) {
-    c->rows = b->rows; c->max_npos = b->max_npos; c->num_work = b->num_work; c->exact = b->lay_exact;
-    c->S_host = b->lay_S;
-    GT_CHECK_ARG(!m->pe || b->lay_meta || b->lay_S > 0, "a caller's token layout needs its S (lay_S or lay_meta) for the positional encoding");
-  } else if (b->sizes_host) {
-    std::vector<int64_t> kv;
-    const HostLayout h = layout_sizes(b->sizes_host, B, m->max_input_len, cls, &kv);
-    c->rows = h.rows; c->max_npos = h.max_npos; c->num_work = h.num_work; c->exact = 1;
-    c->lay_host = 1;
-    c->S_host = h.S;
-    c->lay_bytes = h.bytes; c->lay_o_last = h.o_last; c->lay_o_work = h.o_work;
-    gt_stage_ring* ring = b->ring;
-    GT_CHECK_ARG(ring && ring->base && ring->slots > 0 && ring->slots <= 64, "host-built layout needs a staging ring");
-    if ((int64_t)h.bytes > ring->slot_bytes) { gt_set_error("gt_model_prepare: layout of %zu bytes exceeds the staging slot", h.bytes); return GT_ERR_WORKSPACE; }
-    const int i = ring->next;
-    ring->next = (i + 1) % ring->slots;
-    if (ring->events[i]) (void)hipEventSynchronize((hipEvent_t)ring->events[i]);   // the copy that last read this slot has completed
-    c->stage_ptr = (char*)ring->base + (size_t)i * (size_t)ring->slot_bytes;
-    c->stage_event = ring->events[i];
-    layout_fill(kv, B, h, (char*)c->stage_ptr);
-  } else {   // sizes unknown on the host: gt_seq_layout_packed on the device, upper bounds here
-    c->build_layout_dev = 1;
-    c->rows = N + B * cls;
-    c->max_npos = std::min<int64_t>(m->max_input_len, N) + cls;
-    c->num_work = B + c->rows / 64;
-    c->exact = 0;
-  }
+  GT_TRY(prepare_layout(m, b, c));
   const int64_t rows = c->rows;
 
   // ---- batch descriptors
@@ -411,15 +348,8 @@ extern "C" int gt_model_prepare(const gt_model* m, const gt_model_batch* b, void
     c->prep_ws_bytes = gt_graph_prep_workspace_bytes(N, E, B);
     c->o_prep_ws = a.take(c->prep_ws_bytes);
   }
-  if (c->lay_host) c->o_lay = a.take(c->lay_bytes);
-  if (c->build_layout_dev) {
-    const size_t nd = (size_t)B * 16, nl = (size_t)B * 8, nw = (size_t)std::max<int64_t>(c->num_work, 1) * 8;
-    c->lay_o_last = (nd + 15) / 16 * 16;
-    c->lay_o_work = (c->lay_o_last + nl + 15) / 16 * 16;
-    c->lay_bytes = c->lay_o_work + nw;
-    c->o_lay = a.take(c->lay_bytes);
-    c->o_lay_meta = a.take(16);
-  }
+  if (c->lay_host || c->build_layout_dev) c->o_lay = a.take(c->lay.bytes);
+  if (c->build_layout_dev) c->o_lay_meta = a.take(16);
   c->arena_bytes = std::max(a.off, (size_t)256);
 
   // ---- backward arena
@@ -562,17 +492,17 @@ extern "C" int gt_model_forward(const gt_model* m, void* ctx_, void* arena, floa
   } else {
     char* lay = (char*)P(c->o_lay);
     c->seq_desc = (const int32_t*)lay;
-    c->last_rows = (const int64_t*)(lay + c->lay_o_last);
-    c->work_items = c->num_work ? (const int32_t*)(lay + c->lay_o_work) : nullptr;
+    c->last_rows = (const int64_t*)(lay + c->lay.o_last);
+    c->work_items = c->num_work ? (const int32_t*)(lay + c->lay.o_work) : nullptr;
     if (c->lay_host) {
-      if (hipMemcpyAsync(lay, c->stage_ptr, c->lay_bytes, hipMemcpyHostToDevice, (hipStream_t)st) != hipSuccess) {
+      if (hipMemcpyAsync(lay, c->stage_ptr, c->lay.bytes, hipMemcpyHostToDevice, (hipStream_t)st) != hipSuccess) {
         gt_set_error("gt_model_forward: layout copy failed");
         return GT_ERR_LAUNCH;
       }
       if (c->stage_event) GT_TRY(gt_event_record(c->stage_event, st));
     } else {
-      GT_TRY(gt_seq_layout_packed(graph_ptr, B, m->max_input_len, m->with_cls ? 1 : 0, (int32_t*)lay, (int64_t*)(lay + c->lay_o_last),
-                                  (int32_t*)(lay + c->lay_o_work), c->num_work, (int32_t*)P(c->o_lay_meta), st));
+      GT_TRY(gt_seq_layout_packed(graph_ptr, B, m->max_input_len, m->with_cls ? 1 : 0, (int32_t*)lay, (int64_t*)(lay + c->lay.o_last),
+                                  (int32_t*)(lay + c->lay.o_work), c->num_work, (int32_t*)P(c->o_lay_meta), st));
     }
   }
   for (int i = 0; i < nenc; ++i) { c->enc[i].seq_desc = c->seq_desc; c->enc[i].work_items = c->work_items; }
@@ -1076,17 +1006,38 @@ extern "C" int gt_model_abi_sizes(int64_t* out4) {
   return GT_OK;
 }
 
-// The host half of the packed token layout on its own (what gt_model_prepare writes into its staging slot): meta6 = {rows,
-// max_npos, num_work, offset of last_rows, offset of the work list, total bytes}; out_host == NULL only sizes it.
+// The token layout on the host on its own (what gt_model_prepare writes into its staging slot): meta8 = {rows, max_npos, num_work,
+// offset of last_rows, offset of the work list, total bytes, S, row_stride}; out_host == NULL only sizes it.
+extern "C" int gt_seq_layout_host(int kind, const int64_t* sizes_host, int64_t B, int64_t max_input_len, int with_cls, void* out_host,
+                                  size_t out_bytes, int64_t* meta8) {
+  GT_CHECK_ARG(meta8 && B >= 0 && (sizes_host || !B), "null argument");
+  GT_CHECK_ARG(kind == GT_SEQ_PACKED || kind == GT_SEQ_PADDED, "bad layout kind");
+  const SeqHostLayout h = seq_layout_rank(kind, sizes_host, B, max_input_len, with_cls ? 1 : 0);
+  meta8[0] = h.rows; meta8[1] = h.max_npos; meta8[2] = h.num_work;
+  meta8[3] = (int64_t)h.blob.o_last; meta8[4] = (int64_t)h.blob.o_work; meta8[5] = (int64_t)h.blob.bytes;
+  meta8[6] = h.S; meta8[7] = h.row_stride;
+  if (!out_host) return GT_OK;
+  if (out_bytes < h.blob.bytes) { gt_set_error("gt_seq_layout_host: buffer too small"); return GT_ERR_WORKSPACE; }
+  seq_layout_fill(h, (char*)out_host);
+  return GT_OK;
+}
+
 extern "C" int gt_seq_layout_packed_host(const int64_t* sizes_host, int64_t B, int64_t max_input_len, int with_cls, void* out_host,
                                          size_t out_bytes, int64_t* meta6) {
-  GT_CHECK_ARG(sizes_host && meta6 && B >= 0, "null argument");
-  std::vector<int64_t> kv;
-  const HostLayout h = layout_sizes(sizes_host, B, max_input_len, with_cls ? 1 : 0, &kv);
-  meta6[0] = h.rows; meta6[1] = h.max_npos; meta6[2] = h.num_work;
-  meta6[3] = (int64_t)h.o_last; meta6[4] = (int64_t)h.o_work; meta6[5] = (int64_t)h.bytes;
-  if (!out_host) return GT_OK;
-  if (out_bytes < h.bytes) { gt_set_error("gt_seq_layout_packed_host: buffer too small"); return GT_ERR_WORKSPACE; }
-  layout_fill(kv, B, h, (char*)out_host);
+  GT_CHECK_ARG(meta6, "null argument");
+  int64_t meta8[8] = {};
+  const int rc = gt_seq_layout_host(GT_SEQ_PACKED, sizes_host, B, max_input_len, with_cls, out_host, out_bytes, meta8);
+  std::copy(meta8, meta8 + 6, meta6);
+  return rc;
+}
+
+extern "C" int gt_stage_ring_take(gt_stage_ring* ring, size_t bytes, void** slot, void** event) {
+  GT_CHECK_ARG(ring && ring->base && ring->slots > 0 && ring->slots <= 64 && slot && event, "bad staging ring");
+  if ((int64_t)bytes > ring->slot_bytes) { gt_set_error("gt_stage_ring_take: %zu bytes exceed the staging slot", bytes); return GT_ERR_WORKSPACE; }
+  const int i = ring->next;
+  ring->next = (i + 1) % ring->slots;
+  if (ring->events[i]) (void)hipEventSynchronize((hipEvent_t)ring->events[i]);   // the copy that last read this slot has completed
+  *slot = (char*)ring->base + (size_t)i * (size_t)ring->slot_bytes;
+  *event = ring->events[i];
   return GT_OK;
 }

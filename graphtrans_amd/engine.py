@@ -11,7 +11,7 @@ Covered configuration (everything else keeps using the module path, see `eligibl
   GNN_node / GNN_node_Virtualnode with GCNConv or GINConv layers, Linear(<=4, D), BondEncoder-style
   embedding tables or "zero" edge encoders,
   any gnn_dropout, JK in {last, cat}, ASTNodeEncoder / AtomEncoder / nn.Linear inputs, no perturb;
-  packed token layout (cls / last pooling, no positional encoder, no masked layers), ReLU / GELU post-norm
+  packed token layout (cls / last pooling, with or without the positional encoder, no masked layers), ReLU / GELU post-norm
   encoder layers; stacked max_seq_len heads or a single head.
 Reference call path: trainers/base_trainer.py:29-36 -> models/gnn_transformer.py:88-127 -> modules/gnn_module.py:181-224 ->
 modules/transformer_encoder.py:42-61.
@@ -19,7 +19,6 @@ modules/transformer_encoder.py:42-61.
 import ctypes as C
 import os
 import sys
-import threading
 import weakref
 
 import numpy as np
@@ -27,7 +26,7 @@ import torch
 
 from . import _lib, layers
 from ._lib import GT_BF16, GT_EDGE_LINEAR, GT_EDGE_NONE, GT_EDGE_TABLES, GT_F32
-from .graph import _stream
+from .graph import StageRingDesc, _stream, stage_ring
 
 
 OVERLAP_VN = os.environ.get("GT_OVERLAP_VN", "1") != "0"
@@ -51,10 +50,6 @@ def _c4(n):
 class ImageSet(C.Structure):   # gt_image_set
     _fields_ = [("n_jobs", _i32), ("n_bind", _i32)] + [(k, _vp) for k in ("job_w", "job_N", "job_K", "job_T", "job_img", "bind_w",
                                                                           "bind_N", "bind_K", "bind_f", "bind_t")]
-
-
-class StageRingDesc(C.Structure):   # gt_stage_ring
-    _fields_ = [("base", _vp), ("slot_bytes", _i64), ("slots", _i32), ("next", _i32), ("events", _vp * 64)]
 
 
 class ModelDesc(C.Structure):   # gt_model
@@ -126,27 +121,6 @@ def _side_stream(device, which):
             raise RuntimeError("gt_stream_create failed")
         _SIDE_STREAMS[key] = st
     return st
-
-
-# ---- pinned staging ring for the host-built token layout (one per device; the driver takes a slot per forward) -------------------
-_RINGS = {}
-_RING_LOCK = threading.Lock()
-RING_SLOTS, RING_SLOT_BYTES = 64, 1 << 17
-
-
-def _ring(device):
-    key = torch.device(device).index or 0
-    r = _RINGS.get(key)
-    if r is None:
-        lib = _lib.lib()
-        buf = torch.empty(RING_SLOTS * RING_SLOT_BYTES, dtype=torch.uint8).pin_memory()   # pinning costs ~1 ms: once
-        d = StageRingDesc()
-        d.base, d.slot_bytes, d.slots, d.next = buf.data_ptr(), RING_SLOT_BYTES, RING_SLOTS, 0
-        with torch.cuda.device(device):
-            for i in range(RING_SLOTS):
-                d.events[i] = lib.gt_event_create()
-        r = _RINGS[key] = (d, buf)
-    return r[0]
 
 
 def _arr(ctype, vals):
@@ -1029,11 +1003,11 @@ class _FusedModel(torch.autograd.Function):
         bt.enc_seed = (int(torch.empty((), dtype=torch.int64).random_().item()) & 0xFFFFFFFFFFFFFFFF) if (training and enc.dropout_p > 0) else 0
         hook = _bn_sync_hook(model, plan) if training else None
         bt.sync_bn = int(hook is not None)
-        ring = _ring(plan.dev)
-        bt.ring = C.addressof(ring)
+        ring = stage_ring(plan.dev)   # (the driver takes a slot of it for a host-built token layout)
+        bt.ring = C.addressof(ring.desc)
         cbuf = C.create_string_buffer(plan.ctx_bytes)
         sz = SizesDesc()
-        with _RING_LOCK:
+        with ring.lock:
             _lib.check(lib.gt_model_prepare(plan.cm_ref, C.byref(bt), cbuf, C.byref(sz)), "gt_model_prepare")
         arena = (torch.empty if sz.exact else torch.zeros)(sz.arena_bytes, dtype=torch.uint8, device=plan.dev)
         logits = torch.empty((B, plan.ldy), dtype=torch.float32, device=plan.dev)

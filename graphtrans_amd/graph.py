@@ -5,6 +5,7 @@ Replaces the reference's per-layer `degree(row)` (modules/conv.py:57), its unsor
 `gt_graph_prep`, plus the sequence layouts (`SeqLayout`) that describe how node rows map to
 transformer token rows (padded = the reference's (S,B,d) layout; packed = no padding rows at all).
 """
+import ctypes as C
 import threading
 
 import numpy as np
@@ -96,42 +97,51 @@ class GraphStructure:
         return self._layouts[key]
 
 
-class _StageRing:
-    """ONE pinned host allocation cut into slots (pinning costs ~1 ms per allocation), handed out round robin; a slot is reused
-    only after the H2D copy that last read it has completed (waited for if the host is more than a ring ahead of the device)."""
-    SLOTS, SLOT_BYTES = 64, 1 << 16
+class StageRingDesc(C.Structure):   # gt_stage_ring (include/graphtrans_hip.h; size checked by engine._check_abi)
+    _fields_ = [("base", C.c_void_p), ("slot_bytes", C.c_int64), ("slots", C.c_int32), ("next", C.c_int32), ("events", C.c_void_p * 64)]
 
-    def __init__(self):
+
+class StageRing:
+    """ONE pinned host allocation per device cut into slots (pinning costs ~1 ms per allocation), handed out round robin by
+    gt_stage_ring_take; a slot is reused only after the H2D copy that last read it has completed (its library event, recorded behind
+    that copy, is waited for if the host is more than a ring ahead of the device).  Both paths stage their token layout here: SeqLayout
+    below and gt_model_prepare (engine.py), each under `lock` (autograd's backward threads and data-loader threads build layouts too)."""
+    SLOTS, SLOT_BYTES = 64, 1 << 17
+
+    def __init__(self, device):
+        lib = _lib.lib()
         self.buf = torch.empty(self.SLOTS * self.SLOT_BYTES, dtype=torch.uint8).pin_memory()
-        self.events = [None] * self.SLOTS
-        self.next = 0
+        self.desc = d = StageRingDesc()
+        d.base, d.slot_bytes, d.slots, d.next = self.buf.data_ptr(), self.SLOT_BYTES, self.SLOTS, 0
+        with torch.cuda.device(device):   # the events belong to the ring's device
+            for i in range(self.SLOTS):
+                d.events[i] = lib.gt_event_create()
+        self.lock = threading.Lock()
 
     def take(self, nbytes):
-        if nbytes > self.SLOT_BYTES:
-            return None, None
-        i = self.next
-        self.next = (i + 1) % self.SLOTS
-        if self.events[i] is None:
-            self.events[i] = torch.cuda.Event()
-        else:
-            self.events[i].synchronize()
-        return self.buf[i * self.SLOT_BYTES:(i + 1) * self.SLOT_BYTES], self.events[i]
+        """(the first `nbytes` of the next slot, the library event to record behind the copy that reads them)"""
+        slot, event = C.c_void_p(), C.c_void_p()
+        with self.lock:
+            _lib.check(_lib.lib().gt_stage_ring_take(C.byref(self.desc), nbytes, C.byref(slot), C.byref(event)), "gt_stage_ring_take")
+        off = slot.value - self.desc.base
+        return self.buf[off:off + nbytes], event
 
 
-_RINGS = {}   # one ring per device: its events belong to that device's streams (ADVICE r3: one process-global ring reused events across devices)
-_RINGS_LOCK = threading.Lock()
+_RINGS = {}
+_RINGS_LOCK = threading.Lock()   # held for the table only: a wait on one device's ring does not block another device
 
 
-def _staging(nbytes, device):
-    """(pinned slot, event to record behind the copy that reads it) from the ring of `device`; (None, None) if it does not fit a slot"""
+def stage_ring(device):
     dev = torch.device(device)
     key = dev.index if dev.index is not None else torch.cuda.current_device()
-    with _RINGS_LOCK:   # (autograd's backward threads and data-loader threads build layouts too)
+    with _RINGS_LOCK:
         ring = _RINGS.get(key)
         if ring is None:
-            ring = _RINGS[key] = _StageRing()
-        with torch.cuda.device(key):   # a new slot's event is created on the ring's device
-            return ring.take(nbytes)
+            ring = _RINGS[key] = StageRing(key)
+    return ring
+
+
+_KINDS = {"packed": 0, "padded": 1}   # enum gt_seq_kind
 
 
 class SeqLayout:
@@ -169,93 +179,45 @@ class SeqLayout:
         return self
 
     def __init__(self, gs, kind, max_input_len, with_cls):
-        n = gs.sizes
-        B = gs.B
-        cls = 1 if with_cls else 0
-        S = int(min(int(n.max()) if B else 0, max_input_len))  # modules/utils.py:16
-        kept = np.minimum(n, S)
-        kv_len = kept + cls
-        desc = np.zeros((B, 4), dtype=np.int32)
-        if kind == "padded":
-            npos = S + cls
-            desc[:, 0] = np.arange(B)
-            desc[:, 1] = npos
-            desc[:, 2] = npos - kv_len
-            desc[:, 3] = kv_len
-            self.row_stride, self.rows, self.max_npos = B, npos * B, npos
-        elif kind == "packed":
-            tok_ptr = np.concatenate([[0], np.cumsum(kv_len)])
-            desc[:, 0] = tok_ptr[:-1]
-            desc[:, 1] = kv_len
-            desc[:, 2] = 0
-            desc[:, 3] = kv_len
-            self.row_stride, self.rows, self.max_npos = 1, int(tok_ptr[-1]), int(kv_len.max()) if B else 0
-            self.tok_ptr = tok_ptr
-        else:
+        if kind not in _KINDS:
             raise ValueError(kind)
-        self.kind, self.with_cls, self.S, self.B = kind, with_cls, S, B
-        self.kept = kept
+        n, B = gs.sizes, gs.B
+        # desc / last_rows / attention work list: ONE blob from the library's host builder (csrc/seq_layout_host.h), sized first and
+        # then written straight into the buffer the H2D copy reads
+        L = _lib.lib()
+        sizes = np.ascontiguousarray(n, dtype=np.int64)
+        args = (_KINDS[kind], sizes.ctypes.data, B, int(max_input_len), 1 if with_cls else 0)
+        meta = (C.c_int64 * 8)()
+        _lib.check(L.gt_seq_layout_host(*args, None, 0, meta), "gt_seq_layout_host")
+        self.rows, self.max_npos, self.num_work, o_l, o_w, nbytes, S, self.row_stride = meta
+        self.kind, self.with_cls, self.S, self.B = kind, with_cls, S, B   # S = min(largest graph, max_input_len): modules/utils.py:16
+        self.kept = np.minimum(n, S)
         self._n = n
-        self.desc_cpu = desc
-        # attention tile list: (sequence, 64-position tile) for every tile that exists (ragged sizes)
-        # Longest sequences FIRST: a block walks all keys (queries) of its sequence tile by tile, so the longest sequence's
-        # blocks are a serial chain several times the typical one (Code2-like: 418 against 126 tokens) -- started last it
-        # was the tail of every attention launch.  The kernels give XCD x the x-th contiguous eighth of the list (one L2 per
-        # sequence) and dispatch each eighth front to back: sequences are dealt to the eighths by length rank, each eighth
-        # holds its own in descending length, padded with {-1, 0} entries (skipped) to equal size.
-        tiles = (desc[:, 1].astype(np.int64) + 63) // 64
-        if B:
-            order = np.argsort(-desc[:, 1].astype(np.int64), kind="stable")
-            xcd = np.arange(B) % 8                              # eighth of the sequence of length rank r
-            perm = order[np.argsort(xcd, kind="stable")]        # = concat(order[x::8] for x in 0..7)
-            xs = np.sort(xcd)                                   # eighth of perm[i]
-            t = tiles[perm]
-            cnt = np.bincount(xs, weights=t, minlength=8).astype(np.int64)   # tiles per eighth
-            wpx = int(cnt.max())
-            tot = int(t.sum())
-            ws = np.repeat(perm, t)
-            first = np.cumsum(t) - t                            # first work item of every sequence
-            wt = np.arange(tot, dtype=np.int64) - np.repeat(first, t)
-            seg0 = np.cumsum(cnt) - cnt                         # first work item of every eighth
-            wx = np.repeat(xs, t)
-            dest = wx * wpx + (np.arange(tot, dtype=np.int64) - seg0[wx])
-            work = np.empty((8 * wpx, 2), np.int32)
-            work[:, 0] = -1
-            work[:, 1] = 0
-            work[dest, 0] = ws
-            work[dest, 1] = wt
+        on_gpu = torch.device(gs.device).type == "cuda"
+        event = None
+        if not on_gpu:
+            hb = torch.empty(nbytes, dtype=torch.uint8)
+        elif nbytes <= StageRing.SLOT_BYTES:
+            # ONE pinned staging slot from the device's ring (pin_memory() per array cost ~30 us each) and ONE non_blocking H2D copy: a
+            # pageable copy would block the host until everything already queued on the stream has drained (a 10 ms/step stall once)
+            hb, event = stage_ring(gs.device).take(nbytes)
+        else:   # (larger than a ring slot: its own pinned buffer)
+            hb = torch.empty(nbytes, dtype=torch.uint8).pin_memory()
+        _lib.check(L.gt_seq_layout_host(*args, hb.data_ptr(), nbytes, meta), "gt_seq_layout_host")
+        nd, nl, nw = B * 16, B * 8, self.num_work * 8
+        self.desc_cpu = hb[:nd].numpy().view(np.int32).reshape(B, 4).copy()   # (owned: the slot is reused later)
+        if on_gpu:
+            with torch.cuda.device(gs.device):
+                db = torch.empty(nbytes, dtype=torch.uint8, device=gs.device)
+                db.copy_(hb, non_blocking=True)
+                if event is not None:   # on the stream of the copy, whatever the caller's current device is
+                    _lib.check(L.gt_event_record(event, torch.cuda.current_stream(gs.device).cuda_stream), "gt_event_record")
         else:
-            work = np.zeros((0, 2), np.int32)
-        self.num_work = int(work.shape[0])
-        # token row of the last position (CLS / last node) of every sequence: the pooled row
-        last_row = desc[:, 0].astype(np.int64) + (desc[:, 1].astype(np.int64) - 1) * self.row_stride
-        if torch.device(gs.device).type == "cuda":
-            # ONE pinned staging buffer from a ring (pin_memory() per array cost ~30 us each) and ONE non_blocking H2D copy: a pageable
-            # copy would block the host until everything already queued on the stream has drained (a 10 ms/step stall once)
-            nd, nl, nw = desc.size * 4, last_row.size * 8, work.size * 4
-            o_l = (nd + 15) // 16 * 16
-            o_w = (o_l + nl + 15) // 16 * 16
-            nbytes = max(o_w + nw, 16)
-            pinned, event = _staging(nbytes, gs.device)
-            if pinned is None:   # (larger than a ring slot: its own pinned buffer)
-                pinned = torch.empty(nbytes, dtype=torch.uint8).pin_memory()
-            hb = pinned.numpy()
-            hb[:nd].view(np.int32)[:] = desc.reshape(-1)
-            hb[o_l:o_l + nl].view(np.int64)[:] = last_row
-            if nw:
-                hb[o_w:o_w + nw].view(np.int32)[:] = work.reshape(-1)
-            db = torch.empty(nbytes, dtype=torch.uint8, device=gs.device)
-            db.copy_(pinned[:nbytes], non_blocking=True)
-            if event is not None:
-                event.record()
-            self._dev = db
-            self.desc = db[:nd].view(torch.int32).view(B, 4)
-            self.last_rows = db[o_l:o_l + nl].view(torch.int64)
-            self.work = db[o_w:o_w + nw].view(torch.int32).view(-1, 2) if self.num_work else None
-        else:
-            self.work = torch.from_numpy(work)
-            self.desc = torch.from_numpy(desc)
-            self.last_rows = torch.from_numpy(last_row)
+            db = hb
+        self._dev = db
+        self.desc = db[:nd].view(torch.int32).view(B, 4)
+        self.last_rows = db[o_l:o_l + nl].view(torch.int64)
+        self.work = db[o_w:o_w + nw].view(torch.int32).view(-1, 2) if self.num_work or not on_gpu else None
 
     def positions(self):
         """int32 [N] (host, exact layouts): the padded position of every node -- pad_batch left-pads to S (modules/utils.py:16-25),

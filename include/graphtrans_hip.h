@@ -949,6 +949,10 @@ typedef struct gt_stage_ring {   /* pinned HOST staging slots for the token layo
   int32_t slots, next;
   void* events[64];              /* gt_event per slot (recorded behind the copy that read the slot); slots <= 64 */
 } gt_stage_ring;
+/* The next slot of the ring, round robin: waits for the slot's event (the copy that last read the slot has completed) if it has one,
+ * then *slot = base + i * slot_bytes, *event = events[i] (the caller records it behind its own copy), next advances.  bytes >
+ * slot_bytes: GT_ERR_WORKSPACE, nothing advances.  Not thread safe: the caller holds the ring's lock. */
+int gt_stage_ring_take(gt_stage_ring* ring, size_t bytes, void** slot, void** event);
 
 typedef struct gt_model {
   int32_t conv /* GT_CONV_GCN | GT_CONV_GIN | GT_CONV_PNA */, L, n_enc, has_vn, jk_cat, residual;
@@ -1040,9 +1044,15 @@ int gt_model_backward(const gt_model* model, void* ctx, const float* dlogits, fl
 int gt_model_grad_ranges(const gt_model* model, int64_t* lo3, int64_t* hi3);
 /* out4 = sizeof {gt_model, gt_model_batch, gt_image_set, gt_stage_ring}: a binding checks its mirror of the layouts */
 int gt_model_abi_sizes(int64_t* out4);
-/* The host half of the packed token layout (what gt_model_prepare stages for its H2D copy) on its own: seq_desc [B][4] at offset 0,
- * last_rows [B] int64 at meta6[3], the attention work list [num_work][2] at meta6[4]; meta6 = {rows, max_npos, num_work, offset of
- * last_rows, offset of the work list, total bytes}.  out_host == NULL: sizes only.  Pure host code (no GPU needed). */
+/* The token layout built on the host (what gt_model_prepare stages for its H2D copy, and what a binding stages for the layer-by-layer
+ * calls): seq_desc [B][4] at offset 0, last_rows [B] int64 (the token row of the last position of every sequence) at meta8[3], the
+ * attention work list [num_work][2] at meta8[4]; meta8 = {rows, max_npos, num_work, offset of last_rows, offset of the work list,
+ * total bytes, S = min(max nodes per graph, max_input_len), row_stride}.  kind: the two layouts of "Sequence layout" above.
+ * out_host == NULL: sizes only.  B == 0 is legal.  Pure host code (no GPU needed). */
+enum gt_seq_kind { GT_SEQ_PACKED = 0, GT_SEQ_PADDED = 1 };
+int gt_seq_layout_host(int kind, const int64_t* sizes_host, int64_t B, int64_t max_input_len, int with_cls, void* out_host,
+                       size_t out_bytes, int64_t* meta8);
+/* gt_seq_layout_host(GT_SEQ_PACKED, ...) with the first six values of its meta */
 int gt_seq_layout_packed_host(const int64_t* sizes_host, int64_t B, int64_t max_input_len, int with_cls, void* out_host,
                               size_t out_bytes, int64_t* meta6);
 /* gt_seq_gather with the CLS row given in fp32 whatever the token dtype (converted while it is written) */
