@@ -310,7 +310,10 @@ extern "C" int gt_model_prepare(const gt_model* m, const gt_model_batch* b, void
   }
   c->T = m->embed_kind != 1 ? m->n_tables : 0;
   for (int t = 0; t < c->T; ++t) c->e_rows[t] = m->table_rows[t];
-  c->esort = (b->will_bwd && m->embed_sorted && m->embed_kind != 1) ? 1 : 0;
+  // (a frozen message-passing stack has no embedding backward, and no dX GEMM below gnn2transformer's weight gradient: neither the node ids
+  // per table row nor the transposed weights are made)
+  const bool frozen = b->gnn_frozen != 0;
+  c->esort = (b->will_bwd && !frozen && m->embed_sorted && m->embed_kind != 1) ? 1 : 0;
   if (c->esort) {
     c->eplan_bytes = gt_embed_sort_plan_bytes(c->T, c->e_rows, N);
     c->esort_ws_bytes = gt_embed_sort_workspace_bytes(c->T, c->e_rows, N);
@@ -332,7 +335,7 @@ extern "C" int gt_model_prepare(const gt_model* m, const gt_model_batch* b, void
   c->o_ws = a.take(ws);
   c->o_ws2 = a.take(ws2);
   const bool have_imgs = b->use_w3 != 0;
-  c->want_wt = (m->conv != GT_CONV_PNA && b->will_bwd && gt_compute_base(c->compute) == GT_F32 && N >= 1024 && (!have_imgs || (!m->has_vn && m->conv == GT_CONV_GCN))) ? 1 : 0;
+  c->want_wt = (m->conv != GT_CONV_PNA && b->will_bwd && !frozen && gt_compute_base(c->compute) == GT_F32 && N >= 1024 && (!have_imgs || (!m->has_vn && m->conv == GT_CONV_GCN))) ? 1 : 0;
   if (c->want_wt) {
     for (int l = 0; l < L; ++l) c->o_wt[l] = a.take((size_t)(m->conv == GT_CONV_GIN ? 2 : 1) * 2 * D * D * 4);
     c->o_g2t_wt = a.take((size_t)d * Kc * 4);
@@ -361,10 +364,11 @@ extern "C" int gt_model_prepare(const gt_model* m, const gt_model_batch* b, void
   c->q_dtok[1] = q.take((size_t)rows * d * tsz);
   c->q_d_hn = q.take((size_t)N * d * tsz);
   c->q_d_cls = q.take((size_t)B * d * tsz);
-  c->q_d_rep = q.take((size_t)N * Kc * 4);
-  c->q_dA = q.take(ND4); c->q_dB = q.take(ND4); c->q_dC = q.take(ND4);
-  c->q_dJ = q.take(m->jk_cat ? ND4 : 0);
-  for (int i = 0; i < 4; ++i) c->q_dvn[i] = q.take((size_t)B * D * 4);
+  // (frozen message-passing stack: the node-row and virtual-node gradients are never made, their slots are empty)
+  c->q_d_rep = q.take(frozen ? 0 : (size_t)N * Kc * 4);
+  c->q_dA = q.take(frozen ? 0 : ND4); c->q_dB = q.take(frozen ? 0 : ND4); c->q_dC = q.take(frozen ? 0 : ND4);
+  c->q_dJ = q.take((m->jk_cat && !frozen) ? ND4 : 0);
+  for (int i = 0; i < 4; ++i) c->q_dvn[i] = q.take(frozen ? 0 : (size_t)B * D * 4);
   size_t enc_ws = 256;
   for (int i = 0; i < nenc; ++i)
     enc_ws = std::max(enc_ws, i == nenc - 1 ? gt_encoder_layer_pooled_workspace_bytes(&c->enc[i]) : gt_encoder_layer_workspace_bytes(&c->enc[i]));
@@ -373,7 +377,7 @@ extern "C" int gt_model_prepare(const gt_model* m, const gt_model_batch* b, void
   size_t emb_ws;
   if (m->embed_kind == 1) {
     emb_ws = gt_linear_bwd_workspace_bytes(c->compute, N, D, Kp);
-    c->q_ne_dw = q.take(Kp != m->ne_K ? (size_t)D * Kp * 4 : 0);
+    c->q_ne_dw = q.take((Kp != m->ne_K && !frozen) ? (size_t)D * Kp * 4 : 0);
   } else if (c->esort) {
     emb_ws = gt_embed_sum_bwd_sorted_workspace_bytes(c->T, N, D);
   } else {
@@ -385,7 +389,7 @@ extern "C" int gt_model_prepare(const gt_model* m, const gt_model_batch* b, void
   c->bn_rows = 0;
   // (not beyond 64 k rows: the statistics ride in the EXACT-fp32 dX kernel -- at the Erdos-Renyi stress' 131 k x 256 x 256 that GEMM is
   // 219 us against 116 us for the bf16x6 kernel + a 50-us partial pass: 17.6 k -> 17.9 k graphs/s without)
-  if (L > 1 && !b->sync_bn && m->conv == GT_CONV_GCN && training && c->gcn[0].dropout_p == 0.f &&
+  if (L > 1 && !frozen && !b->sync_bn && m->conv == GT_CONV_GCN && training && c->gcn[0].dropout_p == 0.f &&
       gt_linear_bwd_bnstats_ok(c->compute, GT_F32, GT_F32, N)) {
     // which kernel will run the layers' dX GEMMs: the register-row bf16x6 kernel (bound images, N >= 12288: one partial row per 128
     // rows, any N, with or without a virtual node -- its epilogue holds the complete d x_l, virtual-node rows included) or the
@@ -412,9 +416,9 @@ extern "C" int gt_model_prepare(const gt_model* m, const gt_model_batch* b, void
   c->q_ws[0] = q.take(c->bws_bytes);
   c->q_ws[1] = q.take(c->bws_bytes);
   c->q_ws2 = q.take(c->ws2_bytes);
-  c->seg_ws_bytes = m->has_vn ? gt_segment_sum_workspace_bytes(N, D) : 0;
+  c->seg_ws_bytes = (m->has_vn && !frozen) ? gt_segment_sum_workspace_bytes(N, D) : 0;
   c->q_ws3 = q.take(c->seg_ws_bytes);
-  c->q_dimg = q.take(m->conv == GT_CONV_PNA ? (size_t)m->pna_n_img * 4 : 0);
+  c->q_dimg = q.take((m->conv == GT_CONV_PNA && !frozen) ? (size_t)m->pna_n_img * 4 : 0);
   {   // room for every weight-gradient GEMM's partials and every LayerNorm's block partials of one backward (an upper bound: a producer
       // that finds the arena full reduces on the spot)
     size_t need = lin_ws + emb_ws + (size_t)(2 * nenc + 2) * ln_ws;
@@ -758,7 +762,18 @@ extern "C" int gt_model_backward(const gt_model* m, void* ctx_, const float* dlo
   Ctx* c = (Ctx*)ctx_;
   GT_CHECK_ARG(c && c->magic == CTX_MAGIC && c->forwarded, "context without a forward");
   GT_CHECK_ARG(dlogits && grads && barena, "null buffer");
-  GT_CHECK_ARG(stages > 0 && stages < 8 && !(stages & c->stages_done), "bad stage mask");
+  GT_CHECK_ARG(stages > 0 && stages < 8, "bad stage mask");
+  // frozen message-passing stack (gt_model_batch::gnn_frozen): stage 1 is the whole backward and closes it; bits 1 and 2 do nothing,
+  // in the same call or in later ones
+  const bool frozen = c->in.gnn_frozen != 0;
+  if (frozen) {
+    if (!(stages & 1)) {
+      GT_CHECK_ARG(c->stages_done & 1, "stage order");
+      return GT_OK;
+    }
+    stages = 7;
+  }
+  GT_CHECK_ARG(!(stages & c->stages_done), "bad stage mask");
   GT_CHECK_ARG(!(stages & 2) || ((stages | c->stages_done) & 1), "stage order");
   GT_CHECK_ARG(!(stages & 4) || ((stages | c->stages_done) & 2), "stage order");
   const gt_model_batch& b = c->in;
@@ -857,7 +872,12 @@ extern "C" int gt_model_backward(const gt_model* m, void* ctx_, const float* dlo
       if (m->cls) GT_TRY(gt_colsum_f32(tdt, Q(c->q_d_cls), B, d, G + m->off_cls, st));
     }
     if (c->g2t_wt && m->st_dw) GT_TRY(gt_stream_wait_event(st, m->ev_wt[1]));   // W^T was written on the overlap stream beside the forward
-    if (c->cat2) {   // d h_list[0] -> dJ, d h_list[-1] -> dA straight from the GEMM
+    if (frozen) {   // weight / bias gradient only (the dW-only form of the same call: same row map, same operands); nothing reads a d node_rep
+      g2t = LinBwd{GT_F32, tdt, compute, c->cat2 ? c->first : c->node_rep, m->g2t_w, d_hn, nullptr, nullptr, nullptr, nullptr, G + m->off_g2t_w,
+                   G + m->off_g2t_b, N, d, Kc, c->cat2 ? D : Kc, d, 1, 0, 0, 0.f, W(), ws_bytes, (hipStream_t)st};
+      if (c->cat2) { g2t.x2 = c->h_last; g2t.x_split = D; g2t.ldx2 = D; }
+      c->dy = nullptr;
+    } else if (c->cat2) {   // d h_list[0] -> dJ, d h_list[-1] -> dA straight from the GEMM
       g2t = LinBwd{GT_F32, tdt, compute, c->first, m->g2t_w, d_hn, nullptr, nullptr, nullptr, Q(c->q_dJ), G + m->off_g2t_w, G + m->off_g2t_b,
                    N, d, 2 * D, D, d, 1, 0, 0, 0.f, W(), ws_bytes, (hipStream_t)st};
       g2t.x2 = c->h_last; g2t.dx2 = Q(c->q_dA); g2t.x_split = D; g2t.ldx2 = D;
@@ -873,9 +893,13 @@ extern "C" int gt_model_backward(const gt_model* m, void* ctx_, const float* dlo
     GT_TRY(lin_bwd(g2t));
     GT_TRY(flush());
     c->stages_done |= 1;
+    if (frozen) {   // the closing joins of stage 4: nothing is left to queue a sum, the overlap section closes in the guard
+      GT_TRY(gt_defer_end());
+      c->stages_done = 7;
+    }
   }
 
-  if (stages & 2) {
+  if ((stages & 2) && !frozen) {
     // ---- message passing, last layer first.  dy = d h_list[l+1]; "extra" = gradient reaching x_l from its consumers other than
     // conv_l: the JK slab (l = 0) and the virtual-node update's pooling (l < L-1)
     void* dy = c->dy;
@@ -967,7 +991,7 @@ extern "C" int gt_model_backward(const gt_model* m, void* ctx_, const float* dlo
     c->stages_done |= 2;
   }
 
-  if (stages & 4) {
+  if ((stages & 4) && !frozen) {
     // ---- input encoder
     void* d_h0 = c->d_h0;
     if (m->embed_kind == 1) {   // dW = d_h0^T x, db = colsum(d_h0); the features need no gradient

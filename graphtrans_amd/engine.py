@@ -12,7 +12,9 @@ Covered configuration (everything else keeps using the module path, see `eligibl
   embedding tables or "zero" edge encoders,
   any gnn_dropout, JK in {last, cat}, ASTNodeEncoder / AtomEncoder / nn.Linear inputs, no perturb;
   packed token layout (cls / last pooling, with or without the positional encoder, no masked layers), ReLU / GELU post-norm
-  encoder layers; stacked max_seq_len heads or a single head.
+  encoder layers; stacked max_seq_len heads or a single head;
+  every parameter trainable, or -- on request, `model.fused_freeze` (--fused_freeze) -- exactly `gnn_node` frozen (freeze_gnn /
+  epoch_callback): the same forward, and a backward that stops behind gnn2transformer's weight gradient (`frozen_pattern`).
 Reference call path: trainers/base_trainer.py:29-36 -> models/gnn_transformer.py:88-127 -> modules/gnn_module.py:181-224 ->
 modules/transformer_encoder.py:42-61.
 """
@@ -79,7 +81,7 @@ class BatchDesc(C.Structure):   # gt_model_batch
                [("rows", _i64), ("max_npos", _i64), ("num_work", _i64), ("lay_exact", _i32), ("pad0_", _i32),
                 ("x", _vp), ("x_stride0", _i64), ("x_stride1", _i64), ("node_depth", _vp), ("depth_stride", _i64), ("edge_attr", _vp),
                 ("zeros_B", _vp), ("ident_B", _vp), ("ptr01", _vp)] + \
-               [(k, _i32) for k in ("training", "compute", "tdt", "will_bwd", "use_w3", "use_w1", "sync_bn", "pad2_")] + \
+               [(k, _i32) for k in ("training", "compute", "tdt", "will_bwd", "use_w3", "use_w1", "sync_bn", "gnn_frozen")] + \
                [("gnn_p", _f32), ("enc_p", _f32), ("gnn_seed", C.c_uint64), ("enc_seed", C.c_uint64), ("ring", _vp),
                 ("lay_S", _i64), ("lay_meta", _vp)]
 
@@ -289,6 +291,7 @@ class _Plan:
         self.views = [self.flat[o:o + p.numel()].view(p.shape) for p, o in self.params]
         self.plist = [p for p, _ in self.params]
         self.param_ptrs = tuple(p.data_ptr() for p in self.plist)
+        self.frozen = None   # set_frozen: which parameters the backward hands gradients to
         # ---- the rest of the static struct
         cm.conv = {"gcn": 0, "gin": 1, "pna": 2}[self.kind]
         cm.L, cm.n_enc, cm.has_vn, cm.jk_cat, cm.residual = L, len(self.enc_layers), int(self.has_vn), int(self.jk_cat), int(bool(gnn.residual))
@@ -362,6 +365,12 @@ class _Plan:
         _lib.check(lib.gt_model_grad_ranges(C.byref(cm), lo, hi), "gt_model_grad_ranges")
         self.ranges = list(zip(lo, hi))
         self.cm_ref = C.byref(cm)
+        # range 0 -- what stage 1 of the backward completes -- holds every parameter outside gnn_node and nothing else
+        tail = self.ranges[0][0]
+        gnn_ids = {id(p) for p in gnn.parameters()}
+        self.gnn_plist = [p for p, o in self.params if o < tail]
+        self.tail_outside_gnn = {id(p) for p in self.gnn_plist} == gnn_ids
+        self.set_frozen(frozen_pattern(model) == "gnn")
 
     def _init_convs(self, gnn, seg):
         from .modules.conv import GINConv
@@ -573,6 +582,19 @@ class _Plan:
             cm.pna_kinds[i] = self._SCALER_KIND[blk]
         cm.pna_avg_log, cm.pna_avg_lin = float(c0.avg_deg["log"]), float(c0.avg_deg["lin"])
 
+    def set_frozen(self, frozen):
+        """The part of the plan that follows `requires_grad`: with gnn_node frozen the backward is stage 1 alone (gt_model_batch::
+        gnn_frozen) and only range 0 of the flat buffer -- the parameters outside gnn_node -- is handed out as `.grad`.  The flat
+        layout, the offsets and the parameters' storage stay as they are."""
+        if frozen and not self.tail_outside_gnn:
+            raise RuntimeError("graphtrans_amd.engine: the gradient buffer's tail does not hold exactly the parameters outside gnn_node")
+        self.frozen = bool(frozen)
+        lo = self.ranges[0][0] if self.frozen else 0
+        self.tparams = [(p, o) for p, o in self.params if o >= lo]
+        self.tlist = [p for p, _ in self.tparams]
+        self.tviews = [v for (_, o), v in zip(self.params, self.views) if o >= lo]
+        self.trigger = self.tlist[0]   # what the autograd node hangs on: a parameter that requires grad (frozen: gnn2transformer.weight)
+
     def _set_min_elems(self):
         self.min_elems = DW_OVERLAP_MIN_ELEMS
         self.cm.dw_overlap_min_elems = DW_OVERLAP_MIN_ELEMS
@@ -642,7 +664,22 @@ def _plan(model):
     pe = getattr(model, "pos_encoder", None)   # (a buffer moves with .to() like the parameters)
     if plan is None or plan.param_ptrs != tuple(p.data_ptr() for p in plan.plist) or plan.pe_ptr != (pe.pe.data_ptr() if pe is not None else 0):
         plan = st["plan"] = _Plan(model)
+    # `eligible` lets through "all trainable" and "exactly gnn_node frozen": one flag tells them apart.  Looked at on every call: a
+    # freeze (or an un-freeze) by hand after a warm-up forward reaches no callback
+    frozen = not plan.gnn_plist[0].requires_grad
+    if frozen != plan.frozen:
+        plan.set_frozen(frozen)
     return plan
+
+
+def frozen_pattern(model):
+    """Which parameters of `model` are frozen (requires_grad == False): "none", "gnn" -- exactly the parameters of model.gnn_node,
+    what epoch_callback's freeze_gnn leaves behind -- or "other" (a single conv, gnn2transformer, gnn_node plus a head, ...).
+    Pure: flags only, no device, no library call."""
+    frozen = {id(p) for p in model.parameters() if not p.requires_grad}
+    if not frozen:
+        return "none"
+    return "gnn" if frozen == {id(p) for p in model.gnn_node.parameters()} else "other"
 
 
 def eligible(model, batched_data, perturb):
@@ -651,7 +688,9 @@ def eligible(model, batched_data, perturb):
         return False
     # the fused node differentiates EVERY parameter and assigns `.grad` itself: any frozen parameter (epoch_callback's freeze_gnn,
     # or a user's requires_grad_(False) on any submodule), any tensor hook on a parameter and a DistributedDataParallel wrapper send
-    # the model through the module path.  All three are looked at on EVERY call (a model may be wrapped or hooked after its first
+    # the model through the module path.  The one exception is opt-in (`model.fused_freeze`): with exactly gnn_node frozen
+    # (`frozen_pattern` == "gnn") the node differentiates the parameters outside it and leaves gnn_node's `.grad` alone.
+    # All three are looked at on EVERY call (a model may be wrapped or hooked after its first
     # fused forward): flags and hooks by one pass over the parameters, the wrapper through a flag that torch's module-registration
     # hook sets at the moment a DistributedDataParallel takes the model as its `.module` (`_note_ddp_wrapper`).
     st = state(model)
@@ -668,7 +707,7 @@ def eligible(model, batched_data, perturb):
         if w() is not None:
             return False
         st["ddp_wrapper"] = None   # the wrapper is gone
-    key = (model.training, torch.is_grad_enabled(), tuple(flags))
+    key = (model.training, torch.is_grad_enabled(), tuple(flags), bool(getattr(model, "fused_freeze", False)))
     cache = st.setdefault("eligible", {})
     ok = cache.get(key)
     if ok is None:
@@ -742,6 +781,12 @@ def _note_ddp_wrapper(parent, name, child):
 
 
 torch.nn.modules.module.register_module_module_registration_hook(_note_ddp_wrapper)
+
+
+def _frozen_ok(model):
+    """every parameter trainable, or -- only with `model.fused_freeze` -- exactly gnn_node frozen"""
+    pat = frozen_pattern(model)
+    return pat == "none" or (pat == "gnn" and bool(getattr(model, "fused_freeze", False)))
 
 
 def _eligible_static(model):
@@ -820,8 +865,10 @@ def _eligible_static(model):
         if any_sync(*bns) and len({id(getattr(b, "sync_group", None)) for b in bns}) != 1:
             return False
         for p in model.parameters():
-            if not (p.is_cuda and p.dtype == torch.float32 and p.is_contiguous() and p.requires_grad):
+            if not (p.is_cuda and p.dtype == torch.float32 and p.is_contiguous()):
                 return False
+        if not _frozen_ok(model):
+            return False
     except Exception:
         return False
     return True
@@ -876,8 +923,10 @@ def _eligible_static_pna(model):
         if any_sync(*bns) and len({id(getattr(b, "sync_group", None)) for b in bns}) != 1:
             return False
         for p in model.parameters():
-            if not (p.is_cuda and p.dtype == torch.float32 and p.is_contiguous() and p.requires_grad):
+            if not (p.is_cuda and p.dtype == torch.float32 and p.is_contiguous()):
                 return False
+        if not _frozen_ok(model):
+            return False
     except Exception:
         return False
     return True
@@ -1003,6 +1052,7 @@ class _FusedModel(torch.autograd.Function):
         bt.enc_seed = (int(torch.empty((), dtype=torch.int64).random_().item()) & 0xFFFFFFFFFFFFFFFF) if (training and enc.dropout_p > 0) else 0
         hook = _bn_sync_hook(model, plan) if training else None
         bt.sync_bn = int(hook is not None)
+        bt.gnn_frozen = int(plan.frozen)
         ring = stage_ring(plan.dev)   # (the driver takes a slot of it for a host-built token layout)
         bt.ring = C.addressof(ring.desc)
         cbuf = C.create_string_buffer(plan.ctx_bytes)
@@ -1022,7 +1072,8 @@ class _FusedModel(torch.autograd.Function):
                     e, hook.error = hook.error, None
                     raise e
         if will_bwd:
-            ctx.state = (plan, cbuf, arena, int(sz.barena_bytes), bool(sz.exact), keep, state(model).get("sync"), hook, B)
+            ctx.state = (plan, cbuf, arena, int(sz.barena_bytes), bool(sz.exact), keep, state(model).get("sync"), hook, B,
+                         (plan.frozen, plan.tparams, plan.tlist, plan.tviews))
         else:
             ctx.state = None
         ctx.set_materialize_grads(False)
@@ -1036,7 +1087,7 @@ class _FusedModel(torch.autograd.Function):
                                "(the saved activations are freed after the first backward)")
         if dlogits is None:
             return None, None, None, None
-        plan, cbuf, arena, barena_bytes, exact, _keep, model_sync, hook, B = s
+        plan, cbuf, arena, barena_bytes, exact, _keep, model_sync, hook, B, (frozen, tparams, plist, tviews) = s
         from . import ops
         lib = _lib.lib()
         dl = dlogits.reshape(B, plan.Nh)
@@ -1044,7 +1095,8 @@ class _FusedModel(torch.autograd.Function):
             dl = dl.to(torch.float32)
         dl = ops._padded_rows(dl, plan.ldy) if plan.ldy != plan.Nh else dl.contiguous()
         # gradients: straight into the persistent flat buffer when nothing has to be accumulated
-        plist = plan.plist
+        # (over the parameters this backward differentiates: all of them, or those outside a frozen gnn_node -- as the forward found
+        # them: the prepared context carries the flag, a freeze between forward and backward changes nothing, as under autograd)
         direct = True
         for p in plist:
             if p.grad is not None:
@@ -1065,14 +1117,16 @@ class _FusedModel(torch.autograd.Function):
                 # stream) while the next stage runs: heads .. gnn2transformer | message passing | input encoder
                 # (the C side keeps its overlap and deferred-reduce sections open between the stage calls on this host thread: a raise
                 # from Python in between -- the collective, the BatchNorm hook -- must not leave them pointing at this step's arena)
+                # (gnn_node frozen: stage 1 is the whole backward and its closing stage -- one range, one collective, no virtual-node stream)
                 staged_open = False
+                stages = (1,) if frozen else (1, 2, 4)
                 try:
-                    for i, stage in enumerate((1, 2, 4)):
-                        staged_open = stage != 4
+                    for i, stage in enumerate(stages):
+                        staged_open = stage != stages[-1]
                         _lib.check(lib.gt_model_backward(*args, stage, st), "gt_model_backward")
                         if stage == 2 and plan.has_vn and plan.side is not None:
                             _call("gt_stream_wait_event", st, plan.cm.ev_vnemb)   # d virtualnode_embedding was reduced on the second stream
-                        if stage != 4:
+                        if stage != stages[-1]:
                             _call("gt_overlap_dw_sync")   # (the last stage joins the weight-gradient stream itself)
                         lo, hi = plan.ranges[i]
                         sync.reduce_flat(flat, lo, hi)
@@ -1089,10 +1143,10 @@ class _FusedModel(torch.autograd.Function):
                     raise e
         # ---- hand the gradients to the parameters
         if direct:
-            for p, v in zip(plist, plan.views):
+            for p, v in zip(plist, tviews):
                 p.grad = v
         else:
-            for (p, o_), v0 in zip(plan.params, plan.views):
+            for p, o_ in tparams:
                 v = flat[o_:o_ + p.numel()].view(p.shape)
                 p.grad = v if p.grad is None else p.grad + v
         ctx.state = None
@@ -1102,4 +1156,4 @@ class _FusedModel(torch.autograd.Function):
 def forward(model, batched_data):
     """logits (B, Nh) [row-padded storage] of the fused path; `model` must be `eligible`."""
     plan = _plan(model)
-    return _FusedModel.apply(plan.plist[0], model, batched_data, plan)
+    return _FusedModel.apply(plan.trigger, model, batched_data, plan)

@@ -42,6 +42,8 @@ class GNNTransformer(BaseModel):
                            help="token rows of the Transformer: packed (no pad rows), padded (the reference layout), auto")
         group.add_argument("--pretrained_gnn", type=str, default=None, help="pretrained gnn_node node embedding path")
         group.add_argument("--freeze_gnn", type=int, default=None, help="Freeze gnn_node weight from epoch `freeze_gnn`")
+        group.add_argument("--fused_freeze", default=False, action="store_true",
+                           help="keep a model whose gnn_node is frozen (freeze_gnn) on the fused step: its backward stops behind gnn2transformer")
 
     @staticmethod
     def name(args):
@@ -70,6 +72,7 @@ class GNNTransformer(BaseModel):
             state_dict = torch.load(args.pretrained_gnn)
             self.gnn_node.load_state_dict(self._gnn_node_state(state_dict["model"]))
         self.freeze_gnn = getattr(args, "freeze_gnn", None)
+        self.fused_freeze = bool(getattr(args, "fused_freeze", False))
 
         gnn_emb_dim = 2 * args.gnn_emb_dim if args.gnn_JK == "cat" else args.gnn_emb_dim
         self.gnn2transformer = nn.Linear(gnn_emb_dim, args.d_model)
@@ -176,9 +179,15 @@ class GNNTransformer(BaseModel):
 
     def epoch_callback(self, epoch):
         if self.freeze_gnn is not None and epoch >= self.freeze_gnn:
+            changed = False
             for param in self.gnn_node.parameters():
+                changed |= param.requires_grad
                 param.requires_grad = False
-            engine.invalidate(self)   # the fused path covers fully trainable models only
+            # a frozen gnn_node sends the model to the module path, unless `fused_freeze` asks for the fused step without the
+            # message-passing backward (engine.frozen_pattern); either way the cached plan / eligibility start over
+            # (later epochs find everything frozen already and keep the plan)
+            if changed:
+                engine.invalidate(self)
 
     def _gnn_node_state(self, state_dict):
         module_name = "gnn_node"

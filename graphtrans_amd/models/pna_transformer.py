@@ -27,6 +27,8 @@ class PNATransformer(BaseModel):
         group = parser.add_argument_group("GNNTransformer - Training Config")
         group.add_argument("--pretrained_gnn", type=str, default=None, help="pretrained gnn_node node embedding path")
         group.add_argument("--freeze_gnn", type=int, default=None, help="Freeze gnn_node weight from epoch `freeze_gnn`")
+        group.add_argument("--fused_freeze", default=False, action="store_true",
+                           help="keep a model whose gnn_node is frozen (freeze_gnn) on the fused step: its backward stops behind gnn2transformer")
 
     @staticmethod
     def name(args):
@@ -51,6 +53,7 @@ class PNATransformer(BaseModel):
             state_dict = torch.load(args.pretrained_gnn)["model"]
             self.gnn_node.load_state_dict({k.split("gnn_node.", 1)[1]: v for k, v in state_dict.items() if "gnn_node." in k})
         self.freeze_gnn = getattr(args, "freeze_gnn", None)
+        self.fused_freeze = bool(getattr(args, "fused_freeze", False))
         gnn_emb_dim = 2 * args.gnn_emb_dim if args.gnn_JK == "cat" else args.gnn_emb_dim
         self.gnn2transformer = nn.Linear(gnn_emb_dim, args.d_model)
         self.transformer_encoder = TransformerNodeEncoder(args)
@@ -99,7 +102,13 @@ class PNATransformer(BaseModel):
 
     def epoch_callback(self, epoch):
         if self.freeze_gnn is not None and epoch >= self.freeze_gnn:
+            changed = False
             for param in self.gnn_node.parameters():
+                changed |= param.requires_grad
                 param.requires_grad = False
             from .. import engine
-            engine.invalidate(self)   # the fused path covers fully trainable models only
+            # a frozen gnn_node sends the model to the module path, unless `fused_freeze` asks for the fused step without the
+            # message-passing backward (engine.frozen_pattern); either way the cached plan / eligibility start over
+            # (later epochs find everything frozen already and keep the plan)
+            if changed:
+                engine.invalidate(self)

@@ -1017,7 +1017,11 @@ typedef struct gt_model_batch {
   const void* edge_attr;
   const int32_t *zeros_B, *ident_B, *ptr01;   /* [B] zeros, [B] 0..B-1, {0, B} (device, int32) */
   int32_t training, compute /* gt_compute: the fp32-stored GEMMs */, tdt /* token rows */, will_bwd;
-  int32_t use_w3 /* 0 none, 1 gt_model.w3, 2 gt_model.w3_enc */, use_w1, sync_bn /* gt_bn_sync_set hook installed */, pad2_;
+  int32_t use_w3 /* 0 none, 1 gt_model.w3, 2 gt_model.w3_enc */, use_w1, sync_bn /* gt_bn_sync_set hook installed */;
+  /* every parameter of the message-passing stack (input encoder, conv layers, virtual node: the floats below gt_model::off_g2t_w of the
+   * gradient buffer) is frozen: the forward is unchanged (training-mode BatchNorm, dropout) but saves nothing only their backward reads,
+   * and gt_model_backward stops behind gnn2transformer's weight gradient (see there) */
+  int32_t gnn_frozen;
   float gnn_p, enc_p;
   uint64_t gnn_seed, enc_seed;
   gt_stage_ring* ring;
@@ -1037,7 +1041,11 @@ int gt_model_prepare(const gt_model* model, const gt_model_batch* batch, void* c
 /* logits [B][ldy] fp32 */
 int gt_model_forward(const gt_model* model, void* ctx, void* arena, float* logits, gt_stream_t stream);
 /* dlogits [B][ldy] fp32 (pad columns zero); grads: the flat gradient buffer [grad_total] (overwritten);
- * stages: bit 0 heads .. gnn2transformer, bit 1 message passing, bit 2 input encoder + final joins; in order, each once. */
+ * stages: bit 0 heads .. gnn2transformer, bit 1 message passing, bit 2 input encoder + final joins; in order, each once.
+ * With gt_model_batch::gnn_frozen the backward IS stage 1: gnn2transformer contributes its weight / bias gradient only (no dX GEMM),
+ * the stage closes the backward itself (deferred sums flushed, overlap stream joined) and nothing is enqueued on the virtual-node
+ * stream; only the range {off_g2t_w .. grad_total} of `grads` is written (range 0 of gt_model_grad_ranges, which does not change).
+ * Bits 1 and 2 are then accepted -- in the same call (stages = 7) or in later ones -- and do nothing. */
 int gt_model_backward(const gt_model* model, void* ctx, const float* dlogits, float* grads, void* barena, int stages,
                       gt_stream_t stream);
 /* first / one-past-last float of the gradient range each stage completes: {g2t..total, gnn_lo..g2t, 0..gnn_lo} */
