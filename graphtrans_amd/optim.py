@@ -178,6 +178,11 @@ class FusedAdamW(torch.optim.Optimizer):
                                 plan["chunk_local"].data_ptr(), c0, c1 - c0, t0, t1 - t0, arr, float(group["lr"]),
                                 float(beta1), float(beta2), float(group["eps"]), float(group["weight_decay"]), step,
                                 scale_ptr, _stream())
+            # one step on OTHER gradient tensors (an accumulated step: the fused backward hands out fresh sums) does not evict a cache
+            # whose own tensors are still alive -- the persistent views come back at the next direct step.  Only after a uniform
+            # step: the fast path relies on one shared step count
+            if uniform and fast is not None and all(r() is not None for r in fast["refs"]):
+                continue
             import weakref
             try:   # weak references: the cache must not keep last step's gradients alive
                 plan["fast"] = dict(refs=[weakref.ref(g) for g in grads], uniform=uniform, chunks=keep_chunks, arrs=keep_arrs) if uniform else None
