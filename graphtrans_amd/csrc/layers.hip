@@ -566,6 +566,7 @@ extern "C" int gt_gcn_layer_bwd(const gt_gcn_layer* L, const void* x, const void
     const GcnSaved ps = gcn_saved(L, const_cast<void*>(L->prev_saved));
     lin.bn_x = (const float*)ps.agg; lin.bn_ldx = L->D; lin.bn_mean = ps.stats; lin.bn_rstd = ps.stats + L->D;
     lin.bn_w = L->prev_bn_w; lin.bn_b = L->prev_bn_b; lin.bn_relu = L->prev_relu; lin.bn_part = L->prev_bn_part;
+    lin.bn_nparts = L->prev_bn_nparts;
   }
   lin.bcast = L->dx_bcast; lin.bcast_idx = L->dx_bcast_idx;
   GT_TRY(lin_bwd(lin));

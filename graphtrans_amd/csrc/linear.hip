@@ -1128,14 +1128,18 @@ extern "C" int64_t gt_linear_bwd_bnstats_rows(int64_t M) { return gt_cdiv(M, W32
 // (only with gt_option_set("bnstats_rows_kernel", 1): measured slower than the separate partial pass -- Code2 74.0 k against 74.85 k
 // graphs/s, round 5 -- and gt_linear_bwd_bnstats' documented partial layout is the exact kernel's 64-row tiles; kept as a tested
 // alternative, tests/test_hip_options.py)
-static bool bns_on_rows_kernel(int x_dtype, int y_dtype, const float* weight, int64_t M, int64_t N, int64_t K, int64_t ldx, int64_t ldy) {
-  if (!gt_opt(GT_OPT_BNSTATS_ROWS_KERNEL)) return false;
+// (bns_rows_kernel_can: the shape question alone; the option is read where a caller SIZES the partial buffer -- a call that states the
+// size it was given, LinBwd::bn_nparts, is run by the kernel that fills it and does not read the option again)
+static bool bns_rows_kernel_can(int x_dtype, int y_dtype, const float* weight, int64_t M, int64_t N, int64_t K, int64_t ldx, int64_t ldy) {
   const void* img = w3_lookup(weight, N, K, true);
   if (!img || x_dtype != GT_F32 || y_dtype != GT_F32) return false;
   L32Args w{};
   w.w3 = img;
   w.M = M; w.Nout = K; w.Kc = N; w.lda = ldy; w.ldo = ldx;
   return w3r_ok(GT_F32, GT_F32, w);
+}
+static bool bns_on_rows_kernel(int x_dtype, int y_dtype, const float* weight, int64_t M, int64_t N, int64_t K, int64_t ldx, int64_t ldy) {
+  return gt_opt(GT_OPT_BNSTATS_ROWS_KERNEL) && bns_rows_kernel_can(x_dtype, y_dtype, weight, M, N, K, ldx, ldy);
 }
 extern "C" int64_t gt_linear_bwd_bnstats_rows_for(int compute, int x_dtype, int y_dtype, const float* weight, int64_t M, int64_t N, int64_t K) {
   if (!gt_linear_bwd_bnstats_ok(compute, x_dtype, y_dtype, M)) return 0;
@@ -1332,7 +1336,15 @@ int wide_dx(const LinBwd& c, const BwdState& s, float* wt) {
   hipStream_t stream = c.stream;
   const auto fail = [](const char* msg) { gt_set_error("%s", msg); return GT_ERR_UNSUPPORTED; };
   const void* w3t = (c.y_dtype != GT_F32 && N % 8) ? nullptr : w3_lookup(c.weight, N, K, true);
-  if (w3t && c.bn_part && !bns_on_rows_kernel(c.x_dtype, c.y_dtype, c.weight, M, N, K, c.ldx, c.ldy)) w3t = nullptr;   // the exact kernel's epilogue then
+  if (c.bn_part) {   // which kernel's epilogue sums the statistics: the one that writes as many partial rows as the buffer was sized for
+    // (lin_bwd has checked the count: 0, or one of the two kernels'; where the two coincide it names neither and the option decides)
+    const int64_t rows_kernel = gt_cdiv(M, 128), exact = gt_cdiv(M, W32_BM);
+    bool on_rows = c.bn_nparts == rows_kernel;
+    if (c.bn_nparts == 0 || rows_kernel == exact) on_rows = bns_on_rows_kernel(c.x_dtype, c.y_dtype, c.weight, M, N, K, c.ldx, c.ldy);
+    else if (on_rows && (!w3t || !bns_rows_kernel_can(c.x_dtype, c.y_dtype, c.weight, M, N, K, c.ldx, c.ldy)))
+      return fail("gt_linear_bwd: BatchNorm partials sized for the register-row kernel, which does not take this call");
+    if (!on_rows) w3t = nullptr;   // the exact kernel's epilogue then
+  }
   if (w3t) {
     wt = nullptr;   // the bound image of W^T: k_lin3, no transpose
   } else if (c.weight_t) {
@@ -1576,6 +1588,8 @@ int lin_bwd(const LinBwd& c_) {
     return GT_ERR_UNSUPPORTED;
   }
   LIN_CHECK_ARG(fn, !c.map.add_table, "gt_linear_set_rows_add: forward only (a constant addend has no backward)");
+  LIN_CHECK_ARG(fn, !c.bn_part || c.bn_nparts == 0 || c.bn_nparts == gt_cdiv(c.M, 128) || c.bn_nparts == gt_cdiv(c.M, W32_BM),
+                "BatchNorm partial rows (bn_nparts) fit neither dX kernel: ceil(M / 128) or ceil(M / 64)");
   LIN_CHECK_ARG(fn, !c.map.rows || (c.groups == 1 && !c.y_for_mask && !c.bn_part && !c.map.ln_out &&
                                     rows_eligible(c.compute, c.x_dtype, c.y_dtype, c.weight, c.M, c.N, c.K)),
                 "gt_linear_set_rows: this GEMM does not take a row map (ask gt_linear_rows_ok)");

@@ -63,6 +63,7 @@ struct LinBwd {
   float* bn_part;
   int64_t bn_ldx;
   int bn_relu;
+  int bn_nparts;           // partial rows bn_part was sized for: names the dX kernel (wide_dx); 0 = as the option says at the call
   const float* bcast;      // dX += bcast[bcast_idx[row]] (gt_linear_bwd_bcast)
   const int32_t* bcast_idx;
   // the row operand / the dX as two matrices side by side (gt_linear_bwd_cat2): columns [x_split, K) in x2 / dx2, pitch ldx2

@@ -141,6 +141,29 @@ def _image_set(imgs):
     return s
 
 
+def _rehome(params):
+    """Make `params` views of ONE contiguous storage, in their order (same Parameter objects, same state_dict keys;
+    optim.FusedAdamW notices the move and rebuilds its tables): returns the flat storage and every parameter's offset in it."""
+    with torch.no_grad():
+        flat = torch.cat([p.detach().reshape(-1) for p in params]).contiguous()
+        offs, off = [], 0
+        for p in params:
+            p.data = flat[off:off + p.numel()].view(p.shape)
+            offs.append(off)
+            off += p.numel()
+    return flat, offs
+
+
+def _bn_fields(desc, bn, name="bn", hyper=False):
+    """a descriptor's BatchNorm fields from the module: the running buffers `<name>_rm / _rv / _nbt`; hyper: this is the module
+    whose momentum and eps the descriptor's ONE bn_momentum / bn_eps pair carries"""
+    setattr(desc, name + "_rm", bn.running_mean.data_ptr())
+    setattr(desc, name + "_rv", bn.running_var.data_ptr())
+    setattr(desc, name + "_nbt", bn.num_batches_tracked.data_ptr())
+    if hyper:
+        desc.bn_momentum, desc.bn_eps = float(bn.momentum), float(bn.eps)
+
+
 PNA_TOWER_IMAGES = os.environ.get("GT_PNA_TOWER_IMAGES", "1") != "0"   # bf16x3 images of the PNA tower weights (grouped k_lin3)
 W_MAX_BOUND = 64   # W3_MAX_BOUND / W1_MAX_BOUND of the library's bind tables
 
@@ -179,6 +202,10 @@ class _Plan:
             self.total += _c4(p.numel())
             return off
 
+        def block(ps):
+            """lay out a block of parameters one behind the other: the block's first offset"""
+            return [seg(p) for p in ps][0]
+
         cm = self.cm = ModelDesc()
         ne = gnn.node_encoder
         if hasattr(ne, "type_encoder"):  # ASTNodeEncoder
@@ -206,27 +233,22 @@ class _Plan:
         self.w3_weights = []
         self.etab_flat = None
         if self.kind == "pna":
-            self._init_pna(gnn, seg)
+            self._init_pna(gnn, block)
         else:
-            self._init_convs(gnn, seg)
+            self._init_convs(gnn, seg, block)
         nvn = L - 1 if self.has_vn else 0
         self.vn_desc = (layers.VnUpdateDesc * max(nvn, 1))()
         if self.has_vn:
             for l, seq in enumerate(gnn.mlp_virtualnode_list):
                 m = list(seq)
-                off = None
                 ps = [m[0].weight, m[0].bias, m[1].weight, m[1].bias, m[3].weight, m[3].bias, m[4].weight, m[4].bias]
-                for p in ps:
-                    o = seg(p)
-                    off = o if off is None else off
-                cm.off_vn[l] = off
+                cm.off_vn[l] = block(ps)
                 desc = self.vn_desc[l]
                 desc.D = D
                 for name, p in zip(("w1", "b1", "bn1_w", "bn1_b", "w2", "b2", "bn2_w", "bn2_b"), ps):
                     setattr(desc, name, p.data_ptr())
-                desc.bn1_rm, desc.bn1_rv, desc.bn1_nbt = m[1].running_mean.data_ptr(), m[1].running_var.data_ptr(), m[1].num_batches_tracked.data_ptr()
-                desc.bn2_rm, desc.bn2_rv, desc.bn2_nbt = m[4].running_mean.data_ptr(), m[4].running_var.data_ptr(), m[4].num_batches_tracked.data_ptr()
-                desc.bn_momentum, desc.bn_eps = float(m[1].momentum), float(m[1].eps)
+                _bn_fields(desc, m[1], "bn1", hyper=True)
+                _bn_fields(desc, m[4], "bn2")
         g2t = self.g2t = model.gnn2transformer
         cm.off_g2t_w, cm.off_g2t_b = seg(g2t.weight), seg(g2t.bias)
         self.w3_weights.append(g2t.weight)
@@ -238,12 +260,8 @@ class _Plan:
         self.enc_desc = (layers.EncoderLayerDesc * max(len(self.enc_layers), 1))()
         self.w3_enc_weights = []   # the encoder layers' GEMMs run in fp32 only in the fp32 mode (fp32 token rows)
         for i, mod in enumerate(self.enc_layers):
-            off = None
             ps = layers.encoder_layer_params(mod)
-            for p in ps:
-                o = seg(p)
-                off = o if off is None else off
-            cm.off_enc[i] = off
+            cm.off_enc[i] = block(ps)
             desc = self.enc_desc[i]
             desc.d_model, desc.ffn, desc.nhead = d, mod.linear1.weight.shape[0], enc.nhead
             for name, p in zip(("in_w", "in_b", "out_w", "out_b", "l1_w", "l1_b", "l2_w", "l2_b", "n1_w", "n1_b", "n2_w", "n2_b"), ps):
@@ -275,16 +293,7 @@ class _Plan:
         # parameters' storage IS the stacked matrix -- each head's weight / bias becomes a view of it
         self.head_w_flat, self.head_b_flat = self.heads[0].weight, self.heads[0].bias
         if len(self.heads) > 1:
-            with torch.no_grad():
-                wf = torch.cat([h.weight.detach() for h in self.heads]).contiguous()
-                bf = torch.cat([h.bias.detach() for h in self.heads]).contiguous()
-                r0 = 0
-                for h in self.heads:
-                    n_ = h.weight.shape[0]
-                    h.weight.data = wf[r0:r0 + n_]
-                    h.bias.data = bf[r0:r0 + n_]
-                    r0 += n_
-            self.head_w_flat, self.head_b_flat = wf, bf
+            self.head_w_flat, self.head_b_flat = _rehome([h.weight for h in self.heads])[0], _rehome([h.bias for h in self.heads])[0]
         cm.grad_total = self.total
         # persistent flat gradient buffer and its per-parameter views
         self.flat = torch.zeros(self.total, dtype=torch.float32, device=self.dev)
@@ -372,7 +381,7 @@ class _Plan:
         self.tail_outside_gnn = {id(p) for p in self.gnn_plist} == gnn_ids
         self.set_frozen(frozen_pattern(model) == "gnn")
 
-    def _init_convs(self, gnn, seg):
+    def _init_convs(self, gnn, seg, block):
         from .modules.conv import GINConv
         cm, L, D = self.cm, self.L, self.D
         # ---- conv layers.  Gradient block order of gt_gcn_layer_bwd: lin_w, lin_b, root, edge_w, edge_b, bn_w, bn_b;
@@ -384,15 +393,7 @@ class _Plan:
         self.etab_flat = None
         tabs_all = [[t.weight for t in getattr(conv.edge_encoder, "bond_embedding_list", [])] for conv, _ in self.convs]
         if any(tabs_all):
-            with torch.no_grad():
-                flat = torch.cat([t.detach() for tl in tabs_all for t in tl]).contiguous()
-                r0 = 0
-                for tl in tabs_all:
-                    for t in tl:
-                        n_ = int(t.shape[0])
-                        t.data = flat[r0:r0 + n_]
-                        r0 += n_
-            self.etab_flat = flat
+            self.etab_flat = _rehome([t for tl in tabs_all for t in tl])[0]
         self.conv_desc = ((layers.GinLayerDesc if self.kind == "gin" else layers.GcnLayerDesc) * L)()
         for l, (conv, bn) in enumerate(self.convs):
             desc = self.conv_desc[l]
@@ -411,13 +412,12 @@ class _Plan:
                 m = list(conv.mlp)
                 plist = [conv.eps, *edge, m[0].weight, m[0].bias, m[1].weight, m[1].bias, m[3].weight, m[3].bias, bn.weight, bn.bias]
                 self.w3_weights += [m[0].weight, m[3].weight]
-            off = None
-            for p in plist:
-                o = seg(p)
-                off = o if off is None else off
-                if self.kind == "gin" and p is conv.eps:
-                    self.total = o + 20   # d_eps + the aggregate backward's scratch (GIN_EPS_SLOT in layers.hip)
-            cm.off_conv[l] = off
+            if self.kind == "gin":
+                cm.off_conv[l] = seg(plist.pop(0))
+                self.total = cm.off_conv[l] + 20   # d_eps + the aggregate backward's scratch (GIN_EPS_SLOT in layers.hip)
+                block(plist)
+            else:
+                cm.off_conv[l] = block(plist)
             desc.D = D
             if self.kind == "gcn":
                 desc.lin_w, desc.lin_b, desc.root = conv.linear.weight.data_ptr(), conv.linear.bias.data_ptr(), conv.root_emb.weight.data_ptr()
@@ -425,7 +425,7 @@ class _Plan:
                 desc.eps = conv.eps.data_ptr()
                 desc.w1, desc.b1, desc.bn1_w, desc.bn1_b = m[0].weight.data_ptr(), m[0].bias.data_ptr(), m[1].weight.data_ptr(), m[1].bias.data_ptr()
                 desc.w2, desc.b2 = m[3].weight.data_ptr(), m[3].bias.data_ptr()
-                desc.bn1_rm, desc.bn1_rv, desc.bn1_nbt = m[1].running_mean.data_ptr(), m[1].running_var.data_ptr(), m[1].num_batches_tracked.data_ptr()
+                _bn_fields(desc, m[1], "bn1")
             if mode == "linear":
                 desc.edge_mode = GT_EDGE_LINEAR
                 desc.edge_cols = ee.weight.shape[1]
@@ -441,12 +441,11 @@ class _Plan:
             else:
                 desc.edge_mode = GT_EDGE_NONE
             desc.bn_w, desc.bn_b = bn.weight.data_ptr(), bn.bias.data_ptr()
-            desc.bn_rm, desc.bn_rv, desc.bn_nbt = bn.running_mean.data_ptr(), bn.running_var.data_ptr(), bn.num_batches_tracked.data_ptr()
-            desc.bn_momentum, desc.bn_eps = float(bn.momentum), float(bn.eps)
+            _bn_fields(desc, bn, hyper=True)
 
     _SCALER_KIND = {None: 0, "identity": 0, "amplification": 1, "attenuation": 2, "linear": 3, "inverse_linear": 4}
 
-    def _init_pna(self, gnn, seg):
+    def _init_pna(self, gnn, block):
         """PNANodeEmbedding (modules/pna/pna_module.py:16-78): per layer lin / BatchNorm gradients in the layer block of the flat
         buffer; the tower weights of ALL layers live in one flat storage (the parameters become views of it), from which the driver
         rebuilds the re-stacked images [A ; B], [b | 0], the per-scaler post-Linear blocks and their bias with ONE gather per step."""
@@ -464,28 +463,11 @@ class _Plan:
         # ---- flat tower storage: per layer [pre_w (T,F,2F) | pre_b (T,F) | post_w (T,F,cols) | post_b (T,F)]
         per_layer = T * F * 2 * F + T * F + T * F * cols + T * F
         n_src = L * per_layer
-        with torch.no_grad():
-            flat = torch.empty(n_src, dtype=torch.float32, device=self.dev)
-            off = 0
-            tower_params = []   # (param, offset inside the flat storage)
-            for conv in convs:
-                for group, shape in ((lambda m: m[0].weight, (F, 2 * F)), (lambda m: m[0].bias, (F,))):
-                    for t in range(T):
-                        p = group(conv.pre_nns[t])
-                        n_ = p.numel()
-                        flat[off:off + n_].copy_(p.detach().reshape(-1))
-                        p.data = flat[off:off + n_].view(shape)
-                        tower_params.append((p, off))
-                        off += n_
-                for group, shape in ((lambda m: m[0].weight, (F, cols)), (lambda m: m[0].bias, (F,))):
-                    for t in range(T):
-                        p = group(conv.post_nns[t])
-                        n_ = p.numel()
-                        flat[off:off + n_].copy_(p.detach().reshape(-1))
-                        p.data = flat[off:off + n_].view(shape)
-                        tower_params.append((p, off))
-                        off += n_
-            assert off == n_src
+        towers = [p for conv in convs for nns in (conv.pre_nns, conv.post_nns)
+                  for p in [nn[0].weight for nn in nns] + [nn[0].bias for nn in nns]]
+        flat, offs = _rehome(towers)
+        assert flat.numel() == n_src and tuple(towers[0].shape) == (F, 2 * F) and tuple(towers[2 * T].shape) == (F, cols)
+        tower_params = list(zip(towers, offs))   # (param, offset inside the flat storage)
         self.pna_flat = flat
         # ---- image layout per layer: [pre_stack (T,2F,F) | pre_b2 (T,2F) | Wst (T,S*F,5F) | bst (T,S*F)] and the gather map
         img_per_layer = T * 2 * F * F + T * 2 * F + T * S * F * 5 * F + T * S * F
@@ -536,11 +518,7 @@ class _Plan:
         self.pna_img = torch.zeros(n_img, dtype=torch.float32, device=self.dev)
         # ---- gradient layout: per layer [lin_w, lin_b, bn_w, bn_b] (gt_pna_layer_bwd's order), then the flat tower storage
         for l, (conv, bn) in enumerate(self.convs):
-            off0 = None
-            for p in (conv.lin.weight, conv.lin.bias, bn.weight, bn.bias):
-                o_ = seg(p)
-                off0 = o_ if off0 is None else off0
-            cm.off_conv[l] = off0
+            cm.off_conv[l] = block((conv.lin.weight, conv.lin.bias, bn.weight, bn.bias))
             self.w3_weights.append(conv.lin.weight)
             desc = self.conv_desc[l]
             desc.D, desc.T, desc.S = D, T, S
@@ -550,8 +528,7 @@ class _Plan:
             desc.post_w, desc.post_b = base + 4 * cm.pna_img_off[l][2], base + 4 * cm.pna_img_off[l][3]
             desc.lin_w, desc.lin_b = conv.lin.weight.data_ptr(), conv.lin.bias.data_ptr()
             desc.bn_w, desc.bn_b = bn.weight.data_ptr(), bn.bias.data_ptr()
-            desc.bn_rm, desc.bn_rv, desc.bn_nbt = bn.running_mean.data_ptr(), bn.running_var.data_ptr(), bn.num_batches_tracked.data_ptr()
-            desc.bn_momentum, desc.bn_eps = float(bn.momentum), float(bn.eps)
+            _bn_fields(desc, bn, hyper=True)
         # the towers' re-stacked matrices get bf16x3 images too (grouped k_lin3: the T GEMMs of a tower stack in one launch on the
         # bf16 matrix pipe at fp32 accuracy); views of pna_img, whose contents the driver gathers before it builds the images
         self.pna_tower_views = []
@@ -697,11 +674,9 @@ def eligible(model, batched_data, perturb):
     plist = st.get("params")
     if plist is None:
         plist = st["params"] = list(model.parameters())
-    flags = []
-    for p in plist:
-        if p._backward_hooks or getattr(p, "_post_accumulate_grad_hooks", None):
-            return False
-        flags.append(p.requires_grad)
+    flags = _grad_flags(plist)
+    if flags is None:
+        return False
     w = st.get("ddp_wrapper")   # set by the module-registration hook below when a DistributedDataParallel adopts this model
     if w is not None:
         if w() is not None:
@@ -751,13 +726,20 @@ def eligible(model, batched_data, perturb):
     return True
 
 
+def _grad_flags(params):
+    """requires_grad of every parameter in one pass -- or None when one of them carries a tensor hook (register_hook /
+    register_post_accumulate_grad_hook): the fused node assigns `.grad` itself and would never fire it."""
+    flags = []
+    for p in params:
+        if p._backward_hooks or getattr(p, "_post_accumulate_grad_hooks", None):
+            return None
+        flags.append(p.requires_grad)
+    return flags
+
+
 def has_grad_hooks(model):
-    """Tensor hooks on parameters (register_hook / register_post_accumulate_grad_hook): the fused node assigns `.grad` itself and
-    would never fire them."""
-    for p in model.parameters():
-        if getattr(p, "_backward_hooks", None) or getattr(p, "_post_accumulate_grad_hooks", None):
-            return True
-    return False
+    """Tensor hooks on parameters: see `_grad_flags`."""
+    return _grad_flags(model.parameters()) is None
 
 
 def wrapped_in_ddp(model):
@@ -801,14 +783,6 @@ def _eligible_static(model):
             return False
         if gnn.num_layer > MAXL or len(enc.transformer.layers) > MAXL or len(enc.transformer.layers) < 1:   # the driver's fixed-size tables
             return False
-        ne = gnn.node_encoder
-        if type(ne) is torch.nn.Linear:
-            if ne.bias is None:
-                return False
-        elif not (hasattr(ne, "type_encoder") or hasattr(ne, "atom_embedding_list")):
-            return False
-        if hasattr(ne, "atom_embedding_list") and len(ne.atom_embedding_list) > 16:
-            return False
         D = gnn.convs[0].emb_dim
         if D % 4:
             return False
@@ -846,38 +820,51 @@ def _eligible_static(model):
                 if not (len(m) == 6 and isinstance(m[0], torch.nn.Linear) and isinstance(m[1], BatchNorm1d)
                         and isinstance(m[3], torch.nn.Linear) and isinstance(m[4], BatchNorm1d)):
                     return False
-        if enc.activation not in layers.ENC_ACT or enc.d_model % 8 or enc.compute_dtype not in (torch.float32, torch.bfloat16):
-            return False
-        head_dim_ok = getattr(_lib.lib(), "gt_attn_head_dim_ok", None)   # (None: an A/B library of an earlier revision, GT_LIB_PATH)
-        if head_dim_ok is not None and not head_dim_ok(GT_F32, enc.d_model, enc.nhead):   # (the module path raises the library's own message)
-            return False
-        for mod in enc.transformer.layers:
-            if mod.linear1.weight.shape[0] % 8:
-                return False
         if model.gnn2transformer.weight.shape[1] % 4:
             return False
-        # (synchronised BatchNorm -- statistics over all data-parallel ranks -- runs on this path too: the library's BatchNorm calls
-        # exchange their statistics through dist.BnSyncHook, installed around the pass; all of the model's BatchNorms or none)
-        from .modules.norm import any_sync
-        bns = [m for m in model.modules() if isinstance(m, BatchNorm1d)]
-        if any_sync(*bns) and not all(getattr(b, "sync", False) for b in bns):
-            return False
-        if any_sync(*bns) and len({id(getattr(b, "sync_group", None)) for b in bns}) != 1:
-            return False
-        for p in model.parameters():
-            if not (p.is_cuda and p.dtype == torch.float32 and p.is_contiguous()):
-                return False
-        if not _frozen_ok(model):
-            return False
+        return _eligible_static_rest(model)
     except Exception:
         return False
-    return True
+
+
+def _eligible_static_rest(model):
+    """what every conv kind asks of the rest of the model: node encoder, encoder widths, head dim, FFN width, synchronised BatchNorm,
+    parameter dtype, frozen pattern (called inside the callers' try)"""
+    from .modules.norm import BatchNorm1d, any_sync
+    enc = model.transformer_encoder
+    ne = model.gnn_node.node_encoder
+    if type(ne) is torch.nn.Linear:
+        if ne.bias is None:
+            return False
+    elif not (hasattr(ne, "type_encoder") or hasattr(ne, "atom_embedding_list")):
+        return False
+    if hasattr(ne, "atom_embedding_list") and len(ne.atom_embedding_list) > 16:
+        return False
+    if enc.activation not in layers.ENC_ACT or enc.d_model % 8 or enc.compute_dtype not in (torch.float32, torch.bfloat16):
+        return False
+    head_dim_ok = getattr(_lib.lib(), "gt_attn_head_dim_ok", None)   # (None: an A/B library of an earlier revision, GT_LIB_PATH)
+    if head_dim_ok is not None and not head_dim_ok(GT_F32, enc.d_model, enc.nhead):   # (the module path raises the library's own message)
+        return False
+    for mod in enc.transformer.layers:
+        if mod.linear1.weight.shape[0] % 8:
+            return False
+    # (synchronised BatchNorm -- statistics over all data-parallel ranks -- runs on this path too: the library's BatchNorm calls
+    # exchange their statistics through dist.BnSyncHook, installed around the pass; all of the model's BatchNorms or none)
+    bns = [m for m in model.modules() if isinstance(m, BatchNorm1d)]
+    if any_sync(*bns) and not all(getattr(b, "sync", False) for b in bns):
+        return False
+    if any_sync(*bns) and len({id(getattr(b, "sync_group", None)) for b in bns}) != 1:
+        return False
+    for p in model.parameters():
+        if not (p.is_cuda and p.dtype == torch.float32 and p.is_contiguous()):
+            return False
+    return _frozen_ok(model)
 
 
 def _eligible_static_pna(model):
     """PNATransformer (models/pna_transformer.py:16-118) on the fused path: PNANodeEmbedding with the residual connection, towers
     that divide the input, single-layer pre / post nets, packed token layout."""
-    from .modules.norm import BatchNorm1d, any_sync
+    from .modules.norm import BatchNorm1d
     from .modules.pna.pna_module import PNAConv, _AGG_SLOT
     gnn, enc = model.gnn_node, model.transformer_encoder
     try:
@@ -899,37 +886,11 @@ def _eligible_static_pna(model):
             m = getattr(bn, "module", None)
             if not (isinstance(m, BatchNorm1d) and m.affine and m.track_running_stats and m.momentum is not None):
                 return False
-        ne = gnn.node_encoder
-        if type(ne) is torch.nn.Linear:
-            if ne.bias is None:
-                return False
-        elif not (hasattr(ne, "type_encoder") or hasattr(ne, "atom_embedding_list")):
-            return False
-        if hasattr(ne, "atom_embedding_list") and len(ne.atom_embedding_list) > 16:
-            return False
         if model.gnn2transformer.in_features != c0.in_channels or c0.in_channels % 4 or c0.F_in % 4:
             return False
-        if enc.activation not in layers.ENC_ACT or enc.d_model % 8 or enc.compute_dtype not in (torch.float32, torch.bfloat16):
-            return False
-        head_dim_ok = getattr(_lib.lib(), "gt_attn_head_dim_ok", None)   # (None: an A/B library of an earlier revision, GT_LIB_PATH)
-        if head_dim_ok is not None and not head_dim_ok(GT_F32, enc.d_model, enc.nhead):   # (the module path raises the library's own message)
-            return False
-        for mod in enc.transformer.layers:
-            if mod.linear1.weight.shape[0] % 8:
-                return False
-        bns = [m for m in model.modules() if isinstance(m, BatchNorm1d)]
-        if any_sync(*bns) and not all(getattr(b, "sync", False) for b in bns):
-            return False
-        if any_sync(*bns) and len({id(getattr(b, "sync_group", None)) for b in bns}) != 1:
-            return False
-        for p in model.parameters():
-            if not (p.is_cuda and p.dtype == torch.float32 and p.is_contiguous()):
-                return False
-        if not _frozen_ok(model):
-            return False
+        return _eligible_static_rest(model)
     except Exception:
         return False
-    return True
 
 
 # ---------------------------------------------------------------------------------------------------

@@ -776,12 +776,18 @@ typedef struct gt_gcn_layer {  /* x = h_in [+ vn[batch]]; y = BN(GCNConv(x)) [re
    * layer's `saved` block: same N and D), its affine parameters and ReLU flag, the dX GEMM's epilogue writes the BatchNorm-
    * backward partial sums into prev_bn_part[gt_linear_bwd_bnstats_rows(N)][2][D] (gt_linear_bwd_bnstats; the caller checks
    * gt_linear_bwd_bnstats_ok and that no dropout follows that BatchNorm).  The previous layer's backward then gets the same
-   * buffer as bn_part_in / bn_nparts_in and skips its own statistics pass (gt_batchnorm_bwd_parts). */
+   * buffer as bn_part_in / bn_nparts_in and skips its own statistics pass (gt_batchnorm_bwd_parts).
+   * prev_bn_nparts: the producer-side count, the number of partial rows prev_bn_part was SIZED for -- ceil(N / 64), the exact-fp32
+   * dX kernel's row tiles (gt_linear_bwd_bnstats_rows), or ceil(N / 128), the register-row kernel's blocks
+   * (gt_linear_bwd_bnstats_rows_for).  The dX GEMM runs on the kernel that writes exactly that many rows, whatever the option
+   * "bnstats_rows_kernel" says by then; any other count is GT_ERR_INVALID_ARG.  0 = not stated: the kernel the option names at the
+   * time of the call (the rule of gt_linear_bwd_bnstats). */
   const void* prev_saved;
   const float *prev_bn_w, *prev_bn_b;
   float* prev_bn_part;
   const float* bn_part_in;
   int32_t prev_relu, bn_nparts_in;
+  int32_t prev_bn_nparts, pad_;
   /* forward only, optional gt_event: the graph structure (in_ptr / in_src / in_eid / deg / dis of this descriptor) is being built on
    * another stream (gt_graph_prep beside the input embedding and this layer's GEMM); the forward waits for it between its linear
    * and its aggregate.  NULL = the arrays are ready on `stream`. */
