@@ -16,6 +16,7 @@ LIB_PATH = os.environ.get("GT_LIB_PATH") or os.path.join(_HERE, "libgraphtrans_h
 GT_F32, GT_BF16 = 0, 1
 GT_COMPUTE_F32_HIGH = 2   # enum gt_compute: fp32 compute that allows three bf16 products per fp32 product ("high")
 GT_CONV_GCN, GT_CONV_GIN = 0, 1
+GT_POOL_SUM, GT_POOL_MEAN, GT_POOL_MAX = 1, 2, 3   # enum gt_pool_kind
 GT_EDGE_NONE, GT_EDGE_LINEAR, GT_EDGE_TABLES, GT_EDGE_DENSE = 0, 1, 2, 3
 
 _p = C.c_void_p
@@ -63,6 +64,9 @@ SIGNATURES = {
     "gt_seq_layout_packed": (_i, [_p, _i64, _i64, _i, _p, _p, _p, _i64, _p, _p]),
     "gt_segment_sum_workspace_bytes": (_sz, [_i64, _i64]),
     "gt_segment_sum_ws": (_i, [_i, _p, _p, _p, _i64, _i64, _i64, _p, _p, _sz, _p]),
+    "gt_graph_pool_workspace_bytes": (_sz, [_i, _i64, _i64]),
+    "gt_graph_pool_fwd": (_i, [_i, _i, _p, _p, _i64, _i64, _i64, _p, _p, _p, _sz, _p]),
+    "gt_graph_pool_bwd": (_i, [_i, _i, _p, _p, _p, _p, _i64, _i64, _i64, _p, _p]),
     "gt_seq_gather": (_i, [_i, _p, _p, _p, _p, _i64, _i64, _i64, _i, _i64, _p, _p, _p]),
     "gt_seq_scatter": (_i, [_i, _p, _p, _p, _p, _p, _i64, _i64, _i, _i64, _i64, _p, _p, _p]),
     "gt_batchnorm_workspace_bytes": (_sz, [_i64, _i64]),

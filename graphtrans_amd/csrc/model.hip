@@ -90,6 +90,7 @@ struct Ctx {
   size_t o_h[MAXL + 1], o_x0, o_vn[MAXL], o_vn_saved[MAXL], o_conv_saved[MAXL], o_cat, o_hn, o_tok, o_xin, o_st0, o_xe[MAXL],
       o_enc_saved[MAXL], o_hgin, o_sto, o_eplan, o_esort_ws, o_ne_x, o_ne_w, o_hg, o_ws, o_ws2, o_wt[MAXL], o_g2t_wt;
   size_t o_scales, q_dimg;
+  size_t o_arg, o_pool_ws, pool_ws_bytes;   // read-out mode: the max's winning rows [B][D] int32, gt_graph_pool_fwd's workspace (o_hg: the pooled rows [B][D])
   size_t o_graph_ptr, o_node_graph, o_in_ptr, o_out_ptr, o_idx, o_dd, o_status, o_prep_ws, o_lay, o_lay_meta;
   size_t ws_bytes, ws2_bytes, eplan_bytes, esort_ws_bytes, prep_ws_bytes, arena_bytes;
   int64_t Kc;
@@ -118,13 +119,20 @@ constexpr uint32_t CTX_MAGIC = 0x67744d31u;
 
 int model_check(const char* fn, const gt_model* m) {
   if (!m) { gt_set_error("%s: null model", fn); return GT_ERR_INVALID_ARG; }
-  // (n_enc == 0 is legal in the reference -- it pools the token rows themselves -- but not built here: the callers route it to the module path)
-  if (m->L < 1 || m->L > MAXL || m->n_enc < 1 || m->n_enc > MAXL || m->n_tables < 0 || m->n_tables > MAXT) {
+  // (n_enc == 0 is legal in the reference's GNNTransformer -- it pools the token rows themselves -- but not built here: the callers route it
+  // to the module path.  The read-out mode -- the GNN baseline, gt_model::readout -- has no encoder at all: there n_enc == 0 is required)
+  const bool ro = m->readout != 0;
+  if (m->L < 1 || m->L > MAXL || (ro ? m->n_enc != 0 : (m->n_enc < 1 || m->n_enc > MAXL)) || m->n_tables < 0 || m->n_tables > MAXT) {
     gt_set_error("%s: layer / table counts out of range", fn);
     return GT_ERR_INVALID_ARG;
   }
+  if (ro && ((m->readout != GT_POOL_SUM && m->readout != GT_POOL_MEAN && m->readout != GT_POOL_MAX) || m->jk_cat || m->pe ||
+             (m->conv != GT_CONV_GCN && m->conv != GT_CONV_GIN))) {
+    gt_set_error("%s: the read-out mode takes a GT_POOL_* kind, GCN or GIN layers, JK = last and no positional encoding", fn);
+    return GT_ERR_INVALID_ARG;
+  }
   if (!m->conv_layers || (m->n_enc && !m->enc) || (m->has_vn && m->L > 1 && !m->vn)) { gt_set_error("%s: null descriptor array", fn); return GT_ERR_INVALID_ARG; }
-  if (m->D <= 0 || m->D % 4 || m->d <= 0 || m->d % 8) { gt_set_error("%s: bad widths", fn); return GT_ERR_INVALID_ARG; }
+  if (m->D <= 0 || m->D % 4 || (!ro && (m->d <= 0 || m->d % 8))) { gt_set_error("%s: bad widths", fn); return GT_ERR_INVALID_ARG; }
   if (m->conv != GT_CONV_GCN && m->conv != GT_CONV_GIN && m->conv != GT_CONV_PNA) { gt_set_error("%s: bad conv kind", fn); return GT_ERR_INVALID_ARG; }
   // every position is < S <= max_input_len: a table of at least that many rows needs no clamp in the kernels
   if (m->pe && (m->pe_rows < m->max_input_len || ((uintptr_t)m->pe & 15))) {
@@ -368,7 +376,7 @@ int prepare_decisions(const gt_model* m, const gt_model_batch* b, Ctx* c) {
   k.cat2 = (m->jk_cat && b->use_w3 && gt_linear_cat2_ok(c->compute, m->g2t_w, N, d, D, D)) ? 1 : 0;
   // gnn2transformer's epilogue writes the token rows itself (row map; CLS rows by the map's kernel) when the layout is the packed one
   // built here and the bf16x6 kernel runs it: no pad pass over the node rows (modules/utils.py:5-29), no [N][d] intermediate
-  k.fuse_rows = (!b->seq_desc && gt_linear_rows_ok(c->compute, GT_F32, c->tdt, m->g2t_w, N, d, c->Kc)) ? 1 : 0;
+  k.fuse_rows = (!m->readout && !b->seq_desc && gt_linear_rows_ok(c->compute, GT_F32, c->tdt, m->g2t_w, N, d, c->Kc)) ? 1 : 0;
   // ... and norm_input (transformer_encoder.py:53-57) in the same epilogue when a token row fills one column block of the kernel
   k.fuse_nin = (k.fuse_rows && m->nin_w && gt_linear_rows_layernorm_ok(d)) ? 1 : 0;
   // (a frozen message-passing stack has no embedding backward, and no dX GEMM below gnn2transformer's weight gradient: neither the node ids
@@ -414,10 +422,11 @@ void prepare_forward_arena(const gt_model* m, const gt_model_batch* b, Ctx* c) {
   }
   for (int l = 0; l < L; ++l) c->o_conv_saved[l] = a.take(conv_saved_bytes(m, c, l));
   c->o_cat = a.take((m->jk_cat && !c->k.cat2) ? (size_t)N * Kc * 4 : 0);
-  c->o_hn = a.take((size_t)N * d * (m->pe ? 4 : tsz));   // (fp32 under a positional encoding: its add comes before the one rounding)
-  c->o_rowmap = a.take((size_t)N * 4);
+  const bool ro = m->readout != 0;   // no gnn2transformer, no token rows, no encoder: their slots are empty
+  c->o_hn = a.take(ro ? 0 : (size_t)N * d * (m->pe ? 4 : tsz));   // (fp32 under a positional encoding: its add comes before the one rounding)
+  c->o_rowmap = a.take(ro ? 0 : (size_t)N * 4);
   c->o_pos = a.take(m->pe ? (size_t)N * 4 : 0);
-  c->o_tok = a.take((size_t)rows * d * tsz);
+  c->o_tok = a.take(ro ? 0 : (size_t)rows * d * tsz);
   if (m->nin_w) {
     c->o_xin = a.take((size_t)rows * d * tsz);
     c->o_st0 = a.take((size_t)2 * rows * 4);
@@ -441,7 +450,12 @@ void prepare_forward_arena(const gt_model* m, const gt_model_batch* b, Ctx* c) {
     c->o_ne_x = a.take((size_t)N * Kp * 4);
     c->o_ne_w = a.take((size_t)D * Kp * 4);
   }
-  c->o_hg = a.take((size_t)B * d * 4);
+  c->o_hg = a.take((size_t)B * (ro ? D : d) * 4);
+  if (ro) {
+    c->o_arg = a.take(m->readout == GT_POOL_MAX ? (size_t)B * D * 4 : 0);
+    c->pool_ws_bytes = gt_graph_pool_workspace_bytes(m->readout, N, D);
+    c->o_pool_ws = a.take(c->pool_ws_bytes);
+  }
   if (m->conv == GT_CONV_PNA) c->o_scales = a.take((size_t)N * c->pna[0].S * 4);
   size_t ws = 256, ws2 = 256;
   for (int l = 0; l < L; ++l) ws = std::max(ws, conv_ws_bytes(m, c, l));
@@ -452,7 +466,7 @@ void prepare_forward_arena(const gt_model* m, const gt_model_batch* b, Ctx* c) {
   c->o_ws2 = a.take(ws2);
   if (c->k.want_wt) {
     for (int l = 0; l < L; ++l) c->o_wt[l] = a.take((size_t)conv_gemms(m) * 2 * D * D * 4);
-    c->o_g2t_wt = a.take((size_t)d * Kc * 4);
+    c->o_g2t_wt = a.take(ro ? 0 : (size_t)d * Kc * 4);
   }
   if (c->build_graph) {
     c->o_graph_ptr = a.take((size_t)(B + 1) * 4);
@@ -475,14 +489,16 @@ void prepare_backward_arena(const gt_model* m, const gt_model_batch* b, Ctx* c) 
   const int L = m->L, nenc = m->n_enc;
   const size_t tsz = c->tsz, ND4 = (size_t)N * D * 4;
   const bool frozen = b->gnn_frozen != 0;
+  const bool ro = m->readout != 0;   // heads on the pooled rows [B][D]; the pooling's backward writes d h_list[-1] into q_d_rep
+  const int64_t hk = ro ? D : d;     // the heads' input width
   Bump q;
-  c->q_d_hg = q.take((size_t)B * d * 4);
-  c->q_d_hgin = q.take(m->nout_w ? (size_t)B * d * 4 : 0);
-  c->q_dyp = q.take((size_t)B * d * tsz);
-  c->q_dtok[0] = q.take((size_t)rows * d * tsz);
-  c->q_dtok[1] = q.take((size_t)rows * d * tsz);
-  c->q_d_hn = q.take((size_t)N * d * tsz);
-  c->q_d_cls = q.take((size_t)B * d * tsz);
+  c->q_d_hg = q.take((size_t)B * hk * 4);
+  c->q_d_hgin = q.take((m->nout_w && !ro) ? (size_t)B * d * 4 : 0);
+  c->q_dyp = q.take(ro ? 0 : (size_t)B * d * tsz);
+  c->q_dtok[0] = q.take(ro ? 0 : (size_t)rows * d * tsz);
+  c->q_dtok[1] = q.take(ro ? 0 : (size_t)rows * d * tsz);
+  c->q_d_hn = q.take(ro ? 0 : (size_t)N * d * tsz);
+  c->q_d_cls = q.take(ro ? 0 : (size_t)B * d * tsz);
   // (frozen message-passing stack: the node-row and virtual-node gradients are never made, their slots are empty)
   c->q_d_rep = q.take(frozen ? 0 : (size_t)N * Kc * 4);
   c->q_dA = q.take(frozen ? 0 : ND4); c->q_dB = q.take(frozen ? 0 : ND4); c->q_dC = q.take(frozen ? 0 : ND4);
@@ -491,8 +507,8 @@ void prepare_backward_arena(const gt_model* m, const gt_model_batch* b, Ctx* c) 
   size_t enc_ws = 256;
   for (int i = 0; i < nenc; ++i)
     enc_ws = std::max(enc_ws, i == nenc - 1 ? gt_encoder_layer_pooled_workspace_bytes(&c->enc[i]) : gt_encoder_layer_workspace_bytes(&c->enc[i]));
-  const size_t ln_ws = std::max(gt_layernorm_bwd_workspace_bytes(rows, d), gt_layernorm_bwd_workspace_bytes(B, d));
-  const size_t lin_ws = std::max(gt_linear_bwd_workspace_bytes(c->compute, B, m->Nh, d), gt_linear_bwd_workspace_bytes(c->compute, N, d, Kc));
+  const size_t ln_ws = ro ? 0 : std::max(gt_layernorm_bwd_workspace_bytes(rows, d), gt_layernorm_bwd_workspace_bytes(B, d));
+  const size_t lin_ws = std::max(gt_linear_bwd_workspace_bytes(c->compute, B, m->Nh, hk), ro ? (size_t)0 : gt_linear_bwd_workspace_bytes(c->compute, N, d, Kc));
   const int64_t Kp = (int64_t)c4((size_t)m->ne_K);
   size_t emb_ws;
   if (m->embed_kind == 1) {
@@ -505,7 +521,7 @@ void prepare_backward_arena(const gt_model* m, const gt_model_batch* b, Ctx* c) 
   }
   c->bws_bytes = std::max(std::max(std::max(c->ws_bytes, enc_ws), std::max(ln_ws, lin_ws)), emb_ws);
   for (int l = 0; l + 1 < L; ++l) c->q_bnpart[l] = q.take(c->k.fuse_bn ? (size_t)c->k.bn_rows * 2 * D * 4 : 0);
-  c->heads_ws_bytes = gt_linear_bwd_workspace_bytes(c->compute, B, m->Nh, d);
+  c->heads_ws_bytes = gt_linear_bwd_workspace_bytes(c->compute, B, m->Nh, hk);
   c->q_heads_ws = q.take(c->heads_ws_bytes);
   c->q_ws[0] = q.take(c->bws_bytes);
   c->q_ws[1] = q.take(c->bws_bytes);
@@ -561,8 +577,10 @@ int forward_prologue(const gt_model* m, Ctx* c, gt_stream_t st, void** ev_w1) {
   } else {
     g = Graph{b.graph_ptr, b.node_graph, b.in_ptr, b.in_src, b.in_eid, b.out_ptr, b.out_dst, b.out_eid, b.deg, b.dis};
   }
-  // ---- token layout
-  if (b.seq_desc) {
+  // ---- token layout (none in the read-out mode)
+  if (m->readout) {
+    c->seq_desc = nullptr; c->last_rows = nullptr; c->work_items = nullptr;
+  } else if (b.seq_desc) {
     c->seq_desc = b.seq_desc; c->last_rows = b.last_rows; c->work_items = b.work_items;
   } else {
     char* lay = (char*)P(c->o_lay);
@@ -609,8 +627,9 @@ extern "C" int gt_model_grad_ranges(const gt_model* m, int64_t* lo3, int64_t* hi
   GT_TRY(model_check("gt_model_grad_ranges", m));
   GT_CHECK_ARG(lo3 && hi3, "null output");
   const int64_t gnn_lo = m->has_vn ? m->off_vn_emb : m->off_conv[0];
-  lo3[0] = m->off_g2t_w; hi3[0] = m->grad_total;
-  lo3[1] = gnn_lo;       hi3[1] = m->off_g2t_w;
+  const int64_t tail = m->readout ? m->off_head_w : m->off_g2t_w;   // (read-out mode: no gnn2transformer, the heads follow message passing)
+  lo3[0] = tail;   hi3[0] = m->grad_total;
+  lo3[1] = gnn_lo; hi3[1] = tail;
   lo3[2] = 0;            hi3[2] = gnn_lo;
   return GT_OK;
 }
@@ -629,11 +648,18 @@ extern "C" int gt_model_prepare(const gt_model* m, const gt_model_batch* b, void
   c->tdt = b->tdt;
   c->tsz = gt_elt_bytes(b->tdt);
   c->build_graph = b->graph_ptr == nullptr;
-  GT_TRY(prepare_layout(m, b, c));
-  prepare_descriptors(m, b, c);
-  GT_TRY(prepare_decisions(m, b, c));
-  prepare_forward_arena(m, b, c);
-  prepare_backward_arena(m, b, c);
+  if (m->readout) {   // no token layout (rows = num_work = 0, no staging-ring slot), no encoder weight images
+    GT_CHECK_ARG(!b->gnn_frozen, "the read-out mode has no frozen message-passing stack (models/gnn.py has no freeze_gnn)");
+    c->in.use_w3 = b->use_w3 ? 1 : 0;
+    c->in.use_w1 = 0;
+    c->exact = 1;
+  } else {
+    GT_TRY(prepare_layout(m, b, c));
+  }
+  prepare_descriptors(m, &c->in, c);
+  GT_TRY(prepare_decisions(m, &c->in, c));
+  prepare_forward_arena(m, &c->in, c);
+  prepare_backward_arena(m, &c->in, c);
   c->prepared = 1;
   out->rows = c->rows; out->max_npos = c->max_npos; out->num_work = c->num_work;
   out->arena_bytes = (int64_t)c->arena_bytes; out->barena_bytes = (int64_t)c->barena_bytes;
@@ -670,8 +696,10 @@ extern "C" int gt_model_forward(const gt_model* m, void* ctx_, void* arena, floa
       GT_TRY(gt_stream_wait_event(tst, m->ev_wt[0]));
     }
     for (int l = 0; l < L; ++l) GT_TRY(conv_transpose(m, c, l, (float*)P(c->o_wt[l]), tst));
-    c->g2t_wt = (float*)P(c->o_g2t_wt);
-    GT_TRY(gt_transpose(m->g2t_w, (float*)P(c->o_g2t_wt), d, c->Kc, tst));
+    if (!m->readout) {
+      c->g2t_wt = (float*)P(c->o_g2t_wt);
+      GT_TRY(gt_transpose(m->g2t_w, (float*)P(c->o_g2t_wt), d, c->Kc, tst));
+    }
     if (m->st_dw) GT_TRY(gt_event_record(m->ev_wt[1], tst));
   }
   // ---- input encoder   (dataset/utils.py:28-30 / ogb AtomEncoder / nn.Linear(F, D) dataset/tud.py:65)
@@ -751,6 +779,15 @@ extern "C" int gt_model_forward(const gt_model* m, void* ctx_, void* arena, floa
   }
   c->first = X(0);   // h_list[0] after the in-place virtual-node add
   c->h_last = P(c->o_h[L]);
+  if (m->readout) {
+    // ---- read-out + prediction heads   (models/gnn.py:107-115): the pooled rows [B][D], then one GEMM over the stacked head weights
+    GT_TRY(gt_graph_pool_fwd(m->readout, GT_F32, c->h_last, g.graph_ptr, N, B, D, P(c->o_hg), m->readout == GT_POOL_MAX ? (int32_t*)P(c->o_arg) : nullptr,
+                             P(c->o_pool_ws), c->pool_ws_bytes, st));
+    GT_TRY(gt_linear_fwd_ld(GT_F32, GT_F32, compute, P(c->o_hg), m->head_w, m->head_b, logits, B, m->Nh, D, m->ldy, 0, 0.f, 0, st));
+    if (k.esort && m->st_dw) GT_TRY(gt_stream_wait_event(st, m->ev_sort[1]));   // the closing join of the side streams, as below
+    else if (k.want_wt && m->st_dw) GT_TRY(gt_stream_wait_event(st, m->ev_wt[1]));
+    return GT_OK;
+  }
   if (ev_w1) GT_TRY(gt_stream_wait_event(st, ev_w1));   // the encoder's weight images were built on the prep stream
   // ---- gnn2transformer + token rows + encoder   (models/gnn_transformer.py:92-114)
   void* g2t_out = P(c->o_hn);
@@ -867,6 +904,17 @@ int Bwd::encoder(const float* dlogits, bool frozen) const {
   const int64_t N = c->in.N, B = c->in.B, d = m->d, rows = c->rows;
   const int nenc = m->n_enc, tdt = c->tdt, compute = c->compute;
   const size_t ws_bytes = c->bws_bytes;
+  if (m->readout) {   // heads (dW forked, dX) on the pooled rows [B][D], then the pooling's backward: d h_list[-1] for stage 2
+    const int64_t D = m->D;
+    GT_TRY(gt_linear_bwd_dw_forked(GT_F32, GT_F32, compute, P(c->o_hg), m->head_w, dlogits, nullptr, G + m->off_head_w, G + m->off_head_b, B,
+                                   m->Nh, D, D, m->ldy, 0.f, Q(c->q_heads_ws), c->heads_ws_bytes, st));
+    GT_TRY(gt_linear_bwd_ld(GT_F32, GT_F32, compute, P(c->o_hg), m->head_w, dlogits, nullptr, nullptr, nullptr, Q(c->q_d_hg), nullptr, nullptr,
+                            B, m->Nh, D, m->ldy, 0.f, W(), ws_bytes, st));
+    GT_TRY(gt_graph_pool_bwd(m->readout, GT_F32, Q(c->q_d_hg), m->readout == GT_POOL_MAX ? (const int32_t*)P(c->o_arg) : nullptr, c->g.graph_ptr,
+                             c->g.node_graph, N, B, D, Q(c->q_d_rep), st));
+    c->dy = Q(c->q_d_rep);
+    return flush();
+  }
   // ---- heads: the weight gradient first, forked onto the overlap stream beside the heads' own dX GEMM
   GT_TRY(gt_linear_bwd_dw_forked(GT_F32, GT_F32, compute, P(c->o_hg), m->head_w, dlogits, nullptr, G + m->off_head_w, G + m->off_head_b, B,
                                  m->Nh, d, d, m->ldy, 0.f, Q(c->q_heads_ws), c->heads_ws_bytes, st));

@@ -15,6 +15,9 @@ Covered configuration (everything else keeps using the module path, see `eligibl
   encoder layers; stacked max_seq_len heads or a single head;
   every parameter trainable, or -- on request, `model.fused_freeze` (--fused_freeze) -- exactly `gnn_node` frozen (freeze_gnn /
   epoch_callback): the same forward, and a backward that stops behind gnn2transformer's weight gradient (`frozen_pattern`).
+  The GNN baseline (models/gnn.py: `GNN`) runs the driver's read-out mode (gt_model::readout): the same message-passing stack (GCN /
+  GIN, JK = last), then sum / mean / max pooling per graph and the heads -- no gnn2transformer, token layout, staging ring or encoder
+  weight images; every parameter trainable.
 Reference call path: trainers/base_trainer.py:29-36 -> models/gnn_transformer.py:88-127 -> modules/gnn_module.py:181-224 ->
 modules/transformer_encoder.py:42-61.
 """
@@ -48,6 +51,14 @@ def _c4(n):
     return (n + 3) // 4 * 4
 
 
+def readout_kind(model):
+    """GT_POOL_* of a `models.gnn.GNN` (the driver's read-out mode: message passing -> per-graph pooling -> heads), 0 for the token-path
+    models"""
+    from .models.gnn import GNN
+    from .ops import POOL_KINDS
+    return POOL_KINDS[model.graph_pooling] if isinstance(model, GNN) else 0
+
+
 # ---- mirrors of the driver's structs (include/graphtrans_hip.h; sizes checked against gt_model_abi_sizes at first use) ----------
 class ImageSet(C.Structure):   # gt_image_set
     _fields_ = [("n_jobs", _i32), ("n_bind", _i32)] + [(k, _vp) for k in ("job_w", "job_N", "job_K", "job_T", "job_img", "bind_w",
@@ -71,7 +82,7 @@ class ModelDesc(C.Structure):   # gt_model
                 ("ev_prep_begin", _vp), ("ev_graph", _vp), ("ev_w1", _vp), ("w3", ImageSet), ("w3_enc", ImageSet), ("w1", ImageSet),
                 ("pna_src", _vp), ("pna_img", _vp), ("pna_map", _vp), ("pna_inv", _vp), ("pna_n_img", _i64), ("pna_n_src", _i64),
                 ("off_pna_src", _i64), ("pna_img_off", (_i64 * 4) * MAXL), ("pna_kinds", _i32 * 8), ("pna_avg_log", _f32),
-                ("pna_avg_lin", _f32), ("pe", _vp), ("pe_rows", _i64)]
+                ("pna_avg_lin", _f32), ("readout", _i32), ("pad_readout_", _i32), ("pe", _vp), ("pe_rows", _i64)]
 
 
 class BatchDesc(C.Structure):   # gt_model_batch
@@ -178,7 +189,8 @@ class _Plan:
         from . import w3
         _check_abi()
         lib = _lib.lib()
-        gnn, enc = model.gnn_node, model.transformer_encoder
+        self.readout = readout_kind(model)
+        gnn, enc = model.gnn_node, (None if self.readout else model.transformer_encoder)   # (read-out mode: nothing behind gnn_node but the heads)
         self.L, self.has_vn = gnn.num_layer, isinstance(gnn, GNN_node_Virtualnode)
         if hasattr(gnn, "layers"):   # PNANodeEmbedding
             self.kind = "pna"
@@ -188,7 +200,7 @@ class _Plan:
             self.kind = "gin" if isinstance(gnn.convs[0], GINConv) else "gcn"
             self.D = gnn.convs[0].emb_dim
             self.jk_cat = gnn.JK == "cat"
-        self.d = enc.d_model
+        self.d = self.D if self.readout else enc.d_model   # the heads' input width
         self.dev = next(model.parameters()).device
         self.total = 0
         self.params = []   # (param, offset)
@@ -249,28 +261,13 @@ class _Plan:
                     setattr(desc, name, p.data_ptr())
                 _bn_fields(desc, m[1], "bn1", hyper=True)
                 _bn_fields(desc, m[4], "bn2")
-        g2t = self.g2t = model.gnn2transformer
-        cm.off_g2t_w, cm.off_g2t_b = seg(g2t.weight), seg(g2t.bias)
-        self.w3_weights.append(g2t.weight)
-        self.cls = enc.cls_embedding
-        cm.off_cls = seg(self.cls) if self.cls is not None else -1
-        self.norm_in = enc.norm_input
-        cm.off_nin_w, cm.off_nin_b = (seg(enc.norm_input.weight), seg(enc.norm_input.bias)) if enc.norm_input is not None else (-1, -1)
-        self.enc_layers = list(enc.transformer.layers)
-        self.enc_desc = (layers.EncoderLayerDesc * max(len(self.enc_layers), 1))()
-        self.w3_enc_weights = []   # the encoder layers' GEMMs run in fp32 only in the fp32 mode (fp32 token rows)
-        for i, mod in enumerate(self.enc_layers):
-            ps = layers.encoder_layer_params(mod)
-            cm.off_enc[i] = block(ps)
-            desc = self.enc_desc[i]
-            desc.d_model, desc.ffn, desc.nhead = d, mod.linear1.weight.shape[0], enc.nhead
-            for name, p in zip(("in_w", "in_b", "out_w", "out_b", "l1_w", "l1_b", "l2_w", "l2_b", "n1_w", "n1_b", "n2_w", "n2_b"), ps):
-                setattr(desc, name, p.data_ptr())
-            desc.ln_eps = float(mod.norm1.eps)
-            desc.act = layers.ENC_ACT[enc.activation]
-            self.w3_enc_weights += [mod.self_attn.in_proj_weight, mod.self_attn.out_proj.weight, mod.linear1.weight, mod.linear2.weight]
-        self.norm_out = enc.transformer.norm
-        cm.off_nout_w, cm.off_nout_b = (seg(self.norm_out.weight), seg(self.norm_out.bias)) if self.norm_out is not None else (-1, -1)
+        for k in ("off_g2t_w", "off_g2t_b", "off_cls", "off_nin_w", "off_nin_b", "off_nout_w", "off_nout_b"):
+            setattr(cm, k, -1)
+        self.g2t = self.cls = self.norm_in = self.norm_out = None
+        self.enc_layers, self.w3_enc_weights = [], []
+        self.enc_desc = (layers.EncoderLayerDesc * 1)()
+        if not self.readout:
+            self._init_encoder(model, enc, seg, block)
         if model.max_seq_len is None:
             self.heads = [model.graph_pred_linear]
         else:
@@ -305,7 +302,8 @@ class _Plan:
         cm.conv = {"gcn": 0, "gin": 1, "pna": 2}[self.kind]
         cm.L, cm.n_enc, cm.has_vn, cm.jk_cat, cm.residual = L, len(self.enc_layers), int(self.has_vn), int(self.jk_cat), int(bool(gnn.residual))
         cm.D, cm.d, cm.Nh, cm.ldy = D, d, self.Nh, self.ldy
-        cm.max_input_len = int(enc.max_input_len)
+        cm.readout = self.readout
+        cm.max_input_len = int(enc.max_input_len) if enc is not None else 0
         cm.with_cls = int(self.cls is not None)
         # PositionalEncoding (token_layout="packed" only, see GNNTransformer._use_packed): the module's buffer, read as [max_len][d]
         pe = getattr(model, "pos_encoder", None)
@@ -316,7 +314,7 @@ class _Plan:
         cm.vn_defer_dw = int(VN_DEFER_DW)
         cm.conv_layers = C.cast(self.conv_desc, _vp)
         cm.vn = C.cast(self.vn_desc, _vp) if nvn else None
-        cm.enc = C.cast(self.enc_desc, _vp)
+        cm.enc = C.cast(self.enc_desc, _vp) if self.enc_layers else None
         for t, w in enumerate(self.embed):
             cm.tables[t], cm.table_rows[t], cm.table_clamp[t] = w.data_ptr(), int(w.shape[0]), self.embed_clamp[t]
         # x_0 = h_0 + vn_0[batch] with vn_0 = the ONE row of virtualnode_embedding for every graph (gnn_module.py:195):
@@ -330,7 +328,8 @@ class _Plan:
         cm.vn_emb = self.vn_emb.data_ptr() if self.has_vn else None
         if self.embed_kind == "linear":
             cm.ne_w, cm.ne_b = ne.weight.data_ptr(), ne.bias.data_ptr()
-        cm.g2t_w, cm.g2t_b = g2t.weight.data_ptr(), g2t.bias.data_ptr()
+        if self.g2t is not None:
+            cm.g2t_w, cm.g2t_b = self.g2t.weight.data_ptr(), self.g2t.bias.data_ptr()
         cm.cls = self.cls.data_ptr() if self.cls is not None else None
         if self.norm_in is not None:
             cm.nin_w, cm.nin_b, cm.nin_eps = self.norm_in.weight.data_ptr(), self.norm_in.bias.data_ptr(), float(self.norm_in.eps)
@@ -380,6 +379,32 @@ class _Plan:
         self.gnn_plist = [p for p, o in self.params if o < tail]
         self.tail_outside_gnn = {id(p) for p in self.gnn_plist} == gnn_ids
         self.set_frozen(frozen_pattern(model) == "gnn")
+
+    def _init_encoder(self, model, enc, seg, block):
+        """gnn2transformer, cls / norm_input, the encoder layers and the final norm: gradient offsets and descriptors (token path)"""
+        cm, d = self.cm, self.d
+        g2t = self.g2t = model.gnn2transformer
+        cm.off_g2t_w, cm.off_g2t_b = seg(g2t.weight), seg(g2t.bias)
+        self.w3_weights.append(g2t.weight)
+        self.cls = enc.cls_embedding
+        cm.off_cls = seg(self.cls) if self.cls is not None else -1
+        self.norm_in = enc.norm_input
+        cm.off_nin_w, cm.off_nin_b = (seg(enc.norm_input.weight), seg(enc.norm_input.bias)) if enc.norm_input is not None else (-1, -1)
+        self.enc_layers = list(enc.transformer.layers)
+        self.enc_desc = (layers.EncoderLayerDesc * max(len(self.enc_layers), 1))()
+        self.w3_enc_weights = []   # the encoder layers' GEMMs run in fp32 only in the fp32 mode (fp32 token rows)
+        for i, mod in enumerate(self.enc_layers):
+            ps = layers.encoder_layer_params(mod)
+            cm.off_enc[i] = block(ps)
+            desc = self.enc_desc[i]
+            desc.d_model, desc.ffn, desc.nhead = d, mod.linear1.weight.shape[0], enc.nhead
+            for name, p in zip(("in_w", "in_b", "out_w", "out_b", "l1_w", "l1_b", "l2_w", "l2_b", "n1_w", "n1_b", "n2_w", "n2_b"), ps):
+                setattr(desc, name, p.data_ptr())
+            desc.ln_eps = float(mod.norm1.eps)
+            desc.act = layers.ENC_ACT[enc.activation]
+            self.w3_enc_weights += [mod.self_attn.in_proj_weight, mod.self_attn.out_proj.weight, mod.linear1.weight, mod.linear2.weight]
+        self.norm_out = enc.transformer.norm
+        cm.off_nout_w, cm.off_nout_b = (seg(self.norm_out.weight), seg(self.norm_out.bias)) if self.norm_out is not None else (-1, -1)
 
     def _init_convs(self, gnn, seg, block):
         from .modules.conv import GINConv
@@ -766,8 +791,10 @@ torch.nn.modules.module.register_module_module_registration_hook(_note_ddp_wrapp
 
 
 def _frozen_ok(model):
-    """every parameter trainable, or -- only with `model.fused_freeze` -- exactly gnn_node frozen"""
+    """every parameter trainable, or -- only with `model.fused_freeze`, never in the read-out mode -- exactly gnn_node frozen"""
     pat = frozen_pattern(model)
+    if readout_kind(model):
+        return pat == "none"
     return pat == "none" or (pat == "gnn" and bool(getattr(model, "fused_freeze", False)))
 
 
@@ -775,14 +802,23 @@ def _eligible_static(model):
     from . import ops
     from .modules.conv import GCNConv
     from .modules.norm import BatchNorm1d
-    gnn, enc = model.gnn_node, model.transformer_encoder
-    if hasattr(gnn, "layers"):
-        return _eligible_static_pna(model)
+    gnn = model.gnn_node
     try:
-        if not model._use_packed() or gnn.JK not in ("last", "cat"):
-            return False
-        if gnn.num_layer > MAXL or len(enc.transformer.layers) > MAXL or len(enc.transformer.layers) < 1:   # the driver's fixed-size tables
-            return False
+        ro = readout_kind(model)   # models.gnn.GNN: message passing -> sum / mean / max pooling -> heads (no PNA stack, JK = last only)
+    except Exception:
+        return False
+    if hasattr(gnn, "layers"):
+        return False if ro else _eligible_static_pna(model)
+    try:
+        if ro:
+            if gnn.JK != "last" or gnn.num_layer > MAXL:
+                return False
+        else:
+            enc = model.transformer_encoder
+            if not model._use_packed() or gnn.JK not in ("last", "cat"):
+                return False
+            if gnn.num_layer > MAXL or len(enc.transformer.layers) > MAXL or len(enc.transformer.layers) < 1:   # the driver's fixed-size tables
+                return False
         D = gnn.convs[0].emb_dim
         if D % 4:
             return False
@@ -820,7 +856,7 @@ def _eligible_static(model):
                 if not (len(m) == 6 and isinstance(m[0], torch.nn.Linear) and isinstance(m[1], BatchNorm1d)
                         and isinstance(m[3], torch.nn.Linear) and isinstance(m[4], BatchNorm1d)):
                     return False
-        if model.gnn2transformer.weight.shape[1] % 4:
+        if not ro and model.gnn2transformer.weight.shape[1] % 4:
             return False
         return _eligible_static_rest(model)
     except Exception:
@@ -831,7 +867,6 @@ def _eligible_static_rest(model):
     """what every conv kind asks of the rest of the model: node encoder, encoder widths, head dim, FFN width, synchronised BatchNorm,
     parameter dtype, frozen pattern (called inside the callers' try)"""
     from .modules.norm import BatchNorm1d, any_sync
-    enc = model.transformer_encoder
     ne = model.gnn_node.node_encoder
     if type(ne) is torch.nn.Linear:
         if ne.bias is None:
@@ -840,14 +875,8 @@ def _eligible_static_rest(model):
         return False
     if hasattr(ne, "atom_embedding_list") and len(ne.atom_embedding_list) > 16:
         return False
-    if enc.activation not in layers.ENC_ACT or enc.d_model % 8 or enc.compute_dtype not in (torch.float32, torch.bfloat16):
+    if not readout_kind(model) and not _encoder_ok(model.transformer_encoder):
         return False
-    head_dim_ok = getattr(_lib.lib(), "gt_attn_head_dim_ok", None)   # (None: an A/B library of an earlier revision, GT_LIB_PATH)
-    if head_dim_ok is not None and not head_dim_ok(GT_F32, enc.d_model, enc.nhead):   # (the module path raises the library's own message)
-        return False
-    for mod in enc.transformer.layers:
-        if mod.linear1.weight.shape[0] % 8:
-            return False
     # (synchronised BatchNorm -- statistics over all data-parallel ranks -- runs on this path too: the library's BatchNorm calls
     # exchange their statistics through dist.BnSyncHook, installed around the pass; all of the model's BatchNorms or none)
     bns = [m for m in model.modules() if isinstance(m, BatchNorm1d)]
@@ -859,6 +888,19 @@ def _eligible_static_rest(model):
         if not (p.is_cuda and p.dtype == torch.float32 and p.is_contiguous()):
             return False
     return _frozen_ok(model)
+
+
+def _encoder_ok(enc):
+    """what the encoder kernels ask of a TransformerNodeEncoder: activation, widths, head dim, FFN width"""
+    if enc.activation not in layers.ENC_ACT or enc.d_model % 8 or enc.compute_dtype not in (torch.float32, torch.bfloat16):
+        return False
+    head_dim_ok = getattr(_lib.lib(), "gt_attn_head_dim_ok", None)   # (None: an A/B library of an earlier revision, GT_LIB_PATH)
+    if head_dim_ok is not None and not head_dim_ok(GT_F32, enc.d_model, enc.nhead):   # (the module path raises the library's own message)
+        return False
+    for mod in enc.transformer.layers:
+        if mod.linear1.weight.shape[0] % 8:
+            return False
+    return True
 
 
 def _eligible_static_pna(model):
@@ -920,7 +962,7 @@ class _FusedModel(torch.autograd.Function):
         cm = plan.cm
         if plan.min_elems != DW_OVERLAP_MIN_ELEMS:
             plan._set_min_elems()
-        enc, gnn = model.transformer_encoder, model.gnn_node
+        enc, gnn = (None if plan.readout else model.transformer_encoder), model.gnn_node
         training = bool(model.training)
         bt = BatchDesc()
         x, batch = batched_data.x, batched_data.batch
@@ -938,7 +980,7 @@ class _FusedModel(torch.autograd.Function):
             keep.append(gs)
             if sizes is None:
                 sizes = gs._sizes
-            lay = gs._layouts.get(("packed", int(enc.max_input_len), enc.cls_embedding is not None))
+            lay = None if plan.readout else gs._layouts.get(("packed", int(enc.max_input_len), enc.cls_embedding is not None))
             if lay is not None:
                 bt.seq_desc, bt.last_rows = lay.desc.data_ptr(), lay.last_rows.data_ptr()
                 work = getattr(lay, "work", None)
@@ -992,7 +1034,7 @@ class _FusedModel(torch.autograd.Function):
         # (ops.set_matmul_dtype); the encoder layers compute in bf16 whenever their token rows are stored in bf16
         # (layers.hip: dtype == bf16 ? bf16 : compute), i.e. (fp32, bf16 tokens) is the mixed mode of bench.py
         bf16_mm = ops.get_matmul_dtype() == torch.bfloat16
-        tok_bf16 = enc.compute_dtype == torch.bfloat16
+        tok_bf16 = enc is not None and enc.compute_dtype == torch.bfloat16   # (read-out mode: no token rows; everything is fp32-stored)
         # (ops.set_matmul_precision is read here, at every forward; the prepared context carries it to this forward's backward)
         bt.training, bt.compute, bt.tdt = int(training), ops.f32_compute_code(), (GT_BF16 if tok_bf16 else GT_F32)
         will_bwd = bool(ctx.needs_input_grad[0])
@@ -1009,17 +1051,21 @@ class _FusedModel(torch.autograd.Function):
         from .modules.gnn_module import _gnn_seed
         bt.gnn_seed = _gnn_seed(gnn) & 0xFFFFFFFFFFFFFFFF
         bt.gnn_p = float(gnn.drop_ratio) if training else 0.0
-        bt.enc_p = float(enc.dropout_p) if training else 0.0
-        bt.enc_seed = (int(torch.empty((), dtype=torch.int64).random_().item()) & 0xFFFFFFFFFFFFFFFF) if (training and enc.dropout_p > 0) else 0
+        enc_p = float(enc.dropout_p) if enc is not None else 0.0
+        bt.enc_p = enc_p if training else 0.0
+        bt.enc_seed = (int(torch.empty((), dtype=torch.int64).random_().item()) & 0xFFFFFFFFFFFFFFFF) if (training and enc_p > 0) else 0
         hook = _bn_sync_hook(model, plan) if training else None
         bt.sync_bn = int(hook is not None)
         bt.gnn_frozen = int(plan.frozen)
-        ring = stage_ring(plan.dev)   # (the driver takes a slot of it for a host-built token layout)
-        bt.ring = C.addressof(ring.desc)
         cbuf = C.create_string_buffer(plan.ctx_bytes)
         sz = SizesDesc()
-        with ring.lock:
+        if plan.readout:   # no token layout: no staging ring
             _lib.check(lib.gt_model_prepare(plan.cm_ref, C.byref(bt), cbuf, C.byref(sz)), "gt_model_prepare")
+        else:
+            ring = stage_ring(plan.dev)   # (the driver takes a slot of it for a host-built token layout)
+            bt.ring = C.addressof(ring.desc)
+            with ring.lock:
+                _lib.check(lib.gt_model_prepare(plan.cm_ref, C.byref(bt), cbuf, C.byref(sz)), "gt_model_prepare")
         arena = (torch.empty if sz.exact else torch.zeros)(sz.arena_bytes, dtype=torch.uint8, device=plan.dev)
         logits = torch.empty((B, plan.ldy), dtype=torch.float32, device=plan.dev)
         if hook is not None:

@@ -1,5 +1,6 @@
-"""Model registry for the hot path (models/__init__.py:9-15): `gnn-transformer` and `pna-transformer`; the
-reference's other registry entries are ablation/baseline models outside SURVEY.md §8."""
+"""Model registry (models/__init__.py:9-15): `gnn` (the GCN / GIN baseline with a sum / mean / max read-out), `gnn-transformer`
+and `pna-transformer`.  The reference's other three entries remain out: `pna` (MLP heads), `transformer` and `transformer-gnn`."""
+from .gnn import GNN
 from .gnn_transformer import GNNTransformer
 from .pna_transformer import PNATransformer
 
@@ -10,4 +11,4 @@ def get_model_and_parser(args, parser):
     return model_cls
 
 
-MODELS = {"gnn-transformer": GNNTransformer, "pna-transformer": PNATransformer}
+MODELS = {"gnn": GNN, "gnn-transformer": GNNTransformer, "pna-transformer": PNATransformer}

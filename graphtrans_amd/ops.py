@@ -11,7 +11,7 @@ import os
 import torch
 
 from . import _lib
-from ._lib import GT_BF16, GT_COMPUTE_F32_HIGH, GT_CONV_GCN, GT_CONV_GIN, GT_EDGE_DENSE, GT_EDGE_LINEAR, GT_EDGE_NONE, GT_EDGE_TABLES, GT_F32
+from ._lib import GT_BF16, GT_COMPUTE_F32_HIGH, GT_CONV_GCN, GT_CONV_GIN, GT_EDGE_DENSE, GT_EDGE_LINEAR, GT_EDGE_NONE, GT_EDGE_TABLES, GT_F32, GT_POOL_MAX, GT_POOL_MEAN, GT_POOL_SUM
 from .graph import _ptr, _stream
 
 
@@ -212,6 +212,48 @@ def segment_bcast_add(x, seg, gs):
 
 def segment_sum(x, gs, add=None):
     return _SegmentSum.apply(x, add, gs)
+
+
+POOL_KINDS = {"sum": GT_POOL_SUM, "mean": GT_POOL_MEAN, "max": GT_POOL_MAX}
+
+
+class _GraphPool(torch.autograd.Function):
+    """global_add_pool / global_mean_pool / global_max_pool(x, batch)  (models/gnn.py:64-69, :107)."""
+
+    @staticmethod
+    def forward(ctx, x, gs, kind):
+        x = _dev(x, "x")
+        if x.dim() != 2 or x.shape[0] != gs.N:
+            raise ValueError("graph_pool: x must be [num_nodes, dim]")
+        D = x.shape[1]
+        out = torch.empty((gs.B, D), dtype=x.dtype, device=x.device)
+        arg = torch.empty((gs.B, D), dtype=torch.int32, device=x.device) if kind == GT_POOL_MAX else None
+        ws, wsb = None, 0
+        if gs.N >= 4096:   # load-balanced over row chunks, as _segment_sum_raw
+            wsb = _lib.lib().gt_graph_pool_workspace_bytes(kind, gs.N, D)
+            ws = torch.empty(wsb, dtype=torch.uint8, device=x.device)
+        _lib.launch("gt_graph_pool_fwd", kind, _dtype_code(x), _ptr(x), _ptr(gs.graph_ptr), gs.N, gs.B, D, _ptr(out), _ptr(arg),
+                    _ptr(ws), wsb, _stream())
+        ctx.gs, ctx.kind, ctx.arg = gs, kind, arg
+        return out
+
+    @staticmethod
+    def backward(ctx, g):
+        gs = ctx.gs
+        g = _dev(g, "grad")
+        dx = torch.empty((gs.N, g.shape[1]), dtype=g.dtype, device=g.device)
+        _lib.launch("gt_graph_pool_bwd", ctx.kind, _dtype_code(g), _ptr(g), _ptr(ctx.arg), _ptr(gs.graph_ptr), _ptr(gs.node_graph),
+                    gs.N, gs.B, g.shape[1], _ptr(dx), _stream())
+        return dx, None, None
+
+
+def graph_pool(x, gs, kind):
+    """Per-graph read-out of the node rows x [N][D]: kind in {"sum", "mean", "max"} -> [B][D].  max: the gradient goes to the first
+    maximum in row order (torch_scatter's arg); an empty graph pools to 0."""
+    code = POOL_KINDS.get(kind)
+    if code is None:
+        raise ValueError(f"graph_pool: kind must be one of {sorted(POOL_KINDS)}, got {kind!r}")
+    return _GraphPool.apply(x, gs, code)
 
 
 # ------------------------------------------------------------------------------------------------

@@ -279,6 +279,22 @@ int gt_segment_sum_ws(int dtype, const void* x, const void* add, const int32_t* 
                       int64_t num_graphs, int64_t dim, void* out, void* workspace, size_t workspace_bytes,
                       gt_stream_t stream);
 
+/* Per-graph read-out of node rows (PyG global_add_pool / global_mean_pool / global_max_pool, models/gnn.py:64-69, :107):
+ *   out[b] = sum | mean | max over the rows [graph_ptr[b], graph_ptr[b+1]) of x [N][dim]; storage fp32 or bf16, fp32 accumulation,
+ *   no atomics, fixed reduction order (two runs give the same bits).  mean divides by max(n_b, 1) in the pass that writes `out`.
+ *   max: arg [B][dim] int32 = the node row of the FIRST maximum in row order (torch_scatter's arg); an empty graph gives out = 0,
+ *   arg = -1.  arg is read and written for GT_POOL_MAX only (NULL otherwise).  NaN inputs are out of scope: a NaN never wins a max.
+ * Under the size rule of gt_segment_sum_ws (a workspace of gt_graph_pool_workspace_bytes and num_nodes >= 4096) all three kinds run
+ * load-balanced over row chunks with a per-graph fix-up; otherwise one block per graph and column tile.
+ * gt_graph_pool_bwd: ONE flat pass that writes every element of dx [N][dim] (no zero-fill, no atomics):
+ *   sum dx[n] = d_out[g(n)];  mean dx[n] = d_out[g(n)] * (1 / max(n_g, 1));  max dx[n][c] = arg[g(n)][c] == n ? d_out[g(n)][c] : 0. */
+enum gt_pool_kind { GT_POOL_SUM = 1, GT_POOL_MEAN = 2, GT_POOL_MAX = 3 };
+size_t gt_graph_pool_workspace_bytes(int kind, int64_t num_nodes, int64_t dim);
+int gt_graph_pool_fwd(int kind, int dtype, const void* x, const int32_t* graph_ptr, int64_t num_nodes, int64_t num_graphs,
+                      int64_t dim, void* out, int32_t* arg, void* workspace, size_t workspace_bytes, gt_stream_t stream);
+int gt_graph_pool_bwd(int kind, int dtype, const void* d_out, const int32_t* arg, const int32_t* graph_ptr,
+                      const int32_t* node_graph, int64_t num_nodes, int64_t num_graphs, int64_t dim, void* dx, gt_stream_t stream);
+
 /* ---------------------------------------------------------------------------------------------
  * Sequence layout: flat node rows <-> transformer token rows.
  * Replaces pad_batch / unpad_batch (modules/utils.py:5-53) and the CLS concat
@@ -994,6 +1010,12 @@ typedef struct gt_model {
   int64_t pna_img_off[GT_MODEL_MAX_LAYERS][4];
   int32_t pna_kinds[8];          /* degree scalers of the S output blocks (gt_pna_scales) */
   float pna_avg_log, pna_avg_lin;
+  /* 0: the token path (a caller that zeroes the struct gets it).  GT_POOL_SUM | GT_POOL_MEAN | GT_POOL_MAX: the GNN baseline
+   * (models/gnn.py:98-115) -- message passing, then gt_graph_pool_fwd over h_list[-1] and the heads on the pooled rows [B][D] (head_w is
+   * [Nh][D]).  Requires n_enc == 0, jk_cat == 0, conv GCN or GIN, no pe, gt_model_batch::gnn_frozen == 0; g2t / cls / norm / enc fields
+   * and w3_enc / w1 are not read, no token layout is built (gt_model_sizes: rows = num_work = 0) and no staging-ring slot is taken.
+   * (In front of {pe, pe_rows}, which stay the struct's tail.) */
+  int32_t readout, pad_readout_;
   /* PositionalEncoding (models/gnn_transformer.py:149-168) or NULL: the module's `pe` buffer read as [pe_rows][d] fp32, 16-byte aligned,
    * pe_rows >= max_input_len.  The token row of the node at padded position p (gt_seq_positions) gets + pe[p], in fp32, before its one
    * rounding to the token type; CLS rows get nothing; no gradient. */
@@ -1054,7 +1076,8 @@ int gt_model_forward(const gt_model* model, void* ctx, void* arena, float* logit
  * Bits 1 and 2 are then accepted -- in the same call (stages = 7) or in later ones -- and do nothing. */
 int gt_model_backward(const gt_model* model, void* ctx, const float* dlogits, float* grads, void* barena, int stages,
                       gt_stream_t stream);
-/* first / one-past-last float of the gradient range each stage completes: {g2t..total, gnn_lo..g2t, 0..gnn_lo} */
+/* first / one-past-last float of the gradient range each stage completes: {g2t..total, gnn_lo..g2t, 0..gnn_lo}; with
+ * gt_model::readout (no gnn2transformer) the heads' offset stands where g2t does: {heads..total, gnn_lo..heads, 0..gnn_lo} */
 int gt_model_grad_ranges(const gt_model* model, int64_t* lo3, int64_t* hi3);
 /* out4 = sizeof {gt_model, gt_model_batch, gt_image_set, gt_stage_ring}: a binding checks its mirror of the layouts */
 int gt_model_abi_sizes(int64_t* out4);

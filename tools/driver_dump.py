@@ -109,7 +109,26 @@ def grid():
         g[f"gin:{feat}," + ident(kw)] = mol(kw) if feat == "mol" else code2(kw, 12, 5)
     for kw in ROWS_CASES:
         g["rows:" + ident(kw)] = code2(dict(gnn_emb_dim=128, d_model=128, dim_feedforward=256, **kw), 24, 21, D=128, host_sizes=True)
+    def gnn(kw, B, seed, D=64):   # the read-out mode (gt_model::readout): models.gnn.GNN, no token rows (every mode is fp32-stored)
+        def build(dt):
+            from graphtrans_amd.models.gnn import GNN
+            a = dict(gnn_virtual_node=True, gnn_num_layer=3, gnn_emb_dim=D, gnn_JK="last", gnn_dropout=0.1, gnn_residual=False,
+                     gnn_type="gcn", graph_pooling="mean", max_seq_len=3, model_type="gnn")
+            a.update(kw)
+            from types import SimpleNamespace
+            model = GNN(50, ASTNodeEncoder(D, 98, 300, 20), lambda d: torch.nn.Linear(2, d), SimpleNamespace(**a)).to(DEV)
+            b = synth.code2_like(B=B, seed=seed, num_nodeattributes=300)
+            b._sizes = torch.bincount(b.batch, minlength=B).numpy()
+            b = b.to(DEV)
+            y = labels(B, 5, seed)
+            return model, b, lambda out: losses.code2_loss(out, y)
+        return build
+
     g["pna"] = pna
+    for pool in ("sum", "mean", "max"):
+        for kw in (dict(), dict(gnn_type="gin", gnn_virtual_node=False)):
+            g[f"gnn:{pool}," + ident(kw)] = gnn(dict(graph_pooling=pool, **kw), 12, 5)
+    g["gnn:max,B=128,D=160"] = gnn(dict(graph_pooling="max"), 128, 3, D=160)   # > 4096 rows: the pooling's row chunks, the weight images
     g["frozen"] = code2(dict(fused_freeze=True, gnn_dropout=0.25), 12, 5, frozen=True)
     g["pos_encoder"] = code2(dict(pos_encoder=True, token_layout="packed", gnn_dropout=0.25), 12, 5)
     g["dense:tud"], g["dense:er"] = dense("tud"), dense("er")
@@ -141,10 +160,11 @@ def asked(model, N, mm, dt):
     compute, tdt = ops.f32_compute_code(), GT_BF16 if tok_bf16 else GT_F32
     D, d, Kc = plan.D, plan.d, (2 if plan.jk_cat else 1) * plan.D
     gcn, vn, frozen = plan.kind == "gcn", plan.has_vn, plan.frozen
-    w, w0 = model.gnn2transformer.weight.data_ptr(), plan.w3_weights[0].data_ptr()
+    ro = bool(plan.readout)   # (no gnn2transformer: the two questions about its GEMM are not asked)
+    w, w0 = (0 if ro else model.gnn2transformer.weight.data_ptr()), plan.w3_weights[0].data_ptr()
     with (imgs.bound() if imgs is not None else contextlib.nullcontext()):
-        a = dict(cat2=bool(plan.jk_cat and imgs is not None and L.gt_linear_cat2_ok(compute, w, N, d, D, D)),
-                 fuse_rows=bool(L.gt_linear_rows_ok(compute, GT_F32, tdt, w, N, d, Kc)),
+        a = dict(cat2=bool(not ro and plan.jk_cat and imgs is not None and L.gt_linear_cat2_ok(compute, w, N, d, D, D)),
+                 fuse_rows=bool(not ro and L.gt_linear_rows_ok(compute, GT_F32, tdt, w, N, d, Kc)),
                  bc=bool(gcn and vn and not frozen and L.gt_linear_bwd_bcast_ok(compute, GT_F32, GT_F32, w0, N, D, D)))
         rows = exact = int(L.gt_linear_bwd_bnstats_rows(N))
         if imgs is not None:
