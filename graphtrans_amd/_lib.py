@@ -52,6 +52,7 @@ SIGNATURES = {
     "gt_scale_combine_fwd": (_i, [_p, _p, _i64, _i, _i, _i, _p, _p]),
     "gt_scale_combine_bwd": (_i, [_p, _p, _i64, _i, _i, _i, _p, _p]),
     "gt_embed_sum_fwd": (_i, [_i, _p, _p, _p, _p, _i64, _i64, _p, _p]),
+    "gt_embed_sum_fwd_add": (_i, [_i, _p, _p, _p, _p, _p, _i, _i64, _i64, _p, _p]),
     "gt_embed_sum_bwd_workspace_bytes": (_sz, [_i, _p, _i64]),
     "gt_embed_sum_bwd": (_i, [_i, _p, _p, _p, _p, _p, _i64, _i64, _p, _p, _sz, _p]),
     "gt_embed_sort_plan_bytes": (_sz, [_i, _p, _i64]),
@@ -185,6 +186,7 @@ SIGNATURES = {
     "gt_gin_layer_fwd": (_i, [_p, _p, _p, _p, _p, _p, _p, _sz, _p]),
     "gt_gin_layer_bwd": (_i, [_p, _p, _p, _p, _p, _p, _p, _p, _p, _sz, _p]),
     "gt_add3": (_i, [_p, _p, _p, _i64, _p, _p]),
+    "gt_flag_ascent": (_i, [_p, _p, _i64, _f, _p]),
     "gt_copy2d": (_i, [_p, _i64, _p, _i64, _i64, _i64, _p]),
     "gt_repitch": (_i, [_p, _i64, _p, _i64, _i64, _i, _p]),
     "gt_rows_gather": (_i, [_i, _p, _p, _i64, _i64, _p, _p]),

@@ -30,6 +30,8 @@ struct EmbArgs {
   int64_t row_off[MAX_TABLES]; // bwd: row offset of table t in the concatenated accumulator
   int64_t rows[MAX_TABLES];
   float* dtable[MAX_TABLES];
+  const float* add;     // fwd: optional fp32 [N][D] row operand, summed in behind the first add_before tables (-1: none)
+  int add_before;
   const float* g;
   float* out;
   long long* acc;       // [total_rows][D] int64 fixed point
@@ -47,8 +49,11 @@ __global__ void __launch_bounds__(ET) k_embed_fwd(EmbArgs a) {
   for (int64_t i = (int64_t)blockIdx.x * ET + threadIdx.x; i < total; i += (int64_t)gridDim.x * ET) {
     const int64_t n = i / C, c = (i % C) * 4;
     float4 s = gt_zero4();
-    for (int t = 0; t < a.T; ++t)
+    for (int t = 0; t < a.T; ++t) {
+      if (t == a.add_before) s = gt_add4(s, *reinterpret_cast<const float4*>(a.add + n * a.D + c));
       s = gt_add4(s, *reinterpret_cast<const float4*>(a.table[t] + emb_index(a, t, n) * a.D + c));
+    }
+    if (a.add_before == a.T) s = gt_add4(s, *reinterpret_cast<const float4*>(a.add + n * a.D + c));
     *reinterpret_cast<float4*>(a.out + n * a.D + c) = s;
   }
 }
@@ -446,15 +451,18 @@ int grid_for(int64_t items) {
 
 }  // namespace
 
-extern "C" int gt_embed_sum_fwd(int num_tables, const int64_t* const* idx_ptrs_host, const int64_t* idx_strides_host,
-                                const int64_t* clamp_max_host, const float* const* tables_host, int64_t N, int64_t D,
-                                float* out, gt_stream_t stream_) {
+extern "C" int gt_embed_sum_fwd_add(int num_tables, const int64_t* const* idx_ptrs_host, const int64_t* idx_strides_host,
+                                    const int64_t* clamp_max_host, const float* const* tables_host, const float* add, int add_before,
+                                    int64_t N, int64_t D, float* out, gt_stream_t stream_) {
   int rc = emb_check("gt_embed_sum_fwd", num_tables, N, D);
   if (rc) return rc;
   if (N == 0) return GT_OK;
   GT_CHECK_ARG(idx_ptrs_host && idx_strides_host && clamp_max_host && tables_host && out, "null buffer");
+  GT_CHECK_ARG(!add || (add_before >= 0 && add_before <= num_tables && !((uintptr_t)add & 15)),
+               "the row operand sits behind 0..num_tables tables and is 16-byte aligned");
   EmbArgs a{};
   a.T = num_tables; a.N = N; a.D = D; a.out = out;
+  a.add = add; a.add_before = add ? add_before : -1;
   for (int t = 0; t < num_tables; ++t) {
     a.idx[t] = idx_ptrs_host[t]; a.stride[t] = idx_strides_host[t]; a.clamp[t] = clamp_max_host[t]; a.table[t] = tables_host[t];
     GT_CHECK_ARG(a.idx[t] && a.table[t], "null table / index pointer");
@@ -462,6 +470,12 @@ extern "C" int gt_embed_sum_fwd(int num_tables, const int64_t* const* idx_ptrs_h
   hipLaunchKernelGGL(k_embed_fwd, dim3(grid_for(N * (D / 4))), dim3(ET), 0, (hipStream_t)stream_, a);
   GT_CHECK_LAUNCH();
   return GT_OK;
+}
+
+extern "C" int gt_embed_sum_fwd(int num_tables, const int64_t* const* idx_ptrs_host, const int64_t* idx_strides_host,
+                                const int64_t* clamp_max_host, const float* const* tables_host, int64_t N, int64_t D,
+                                float* out, gt_stream_t stream_) {
+  return gt_embed_sum_fwd_add(num_tables, idx_ptrs_host, idx_strides_host, clamp_max_host, tables_host, nullptr, 0, N, D, out, stream_);
 }
 
 extern "C" size_t gt_embed_sum_bwd_workspace_bytes(int num_tables, const int64_t* table_rows_host, int64_t D) {

@@ -640,6 +640,10 @@ extern "C" int gt_model_prepare(const gt_model* m, const gt_model_batch* b, void
   GT_CHECK_ARG(b && ctx_ && out, "null argument");
   GT_CHECK_ARG(b->N > 0 && b->B > 0 && b->E >= 0, "empty batch");
   GT_CHECK_ARG(b->x && ((b->edge_index && b->batch) || b->graph_ptr), "null batch arrays");
+  // the perturbation of forward(batched_data, perturb) and its gradient (gt_model_batch::perturb / d_perturb)
+  GT_CHECK_ARG(!(b->perturb && b->gnn_frozen), "perturb with gnn_frozen: a frozen message-passing stack hands out no d perturb");
+  GT_CHECK_ARG(!b->d_perturb || (b->perturb && b->will_bwd), "d_perturb without perturb (or without will_bwd)");
+  GT_CHECK_ARG(!(((uintptr_t)b->perturb | (uintptr_t)b->d_perturb) & 15), "perturb / d_perturb must be 16-byte aligned");
   Ctx* c = (Ctx*)ctx_;
   memset(c, 0, sizeof(Ctx));
   c->magic = CTX_MAGIC;
@@ -714,6 +718,8 @@ extern "C" int gt_model_forward(const gt_model* m, void* ctx_, void* arena, floa
     }
     c->ne_x = nx; c->ne_w = nw;
     GT_TRY(gt_linear_fwd(GT_F32, GT_F32, compute, nx, nw, m->ne_b, P(c->o_h[0]), N, D, Kp, 0, 0.f, 0, st));
+    if (b.perturb)   // encoded + perturb (gnn_module.py:158), in place behind the GEMM
+      GT_TRY(gt_add3((const float*)P(c->o_h[0]), b.perturb, nullptr, N * D, (float*)P(c->o_h[0]), st));
   } else {
     const int64_t* x = (const int64_t*)b.x;
     if (m->embed_kind == 2) {   // ASTNodeEncoder: type, attribute, clamped depth
@@ -731,7 +737,8 @@ extern "C" int gt_model_forward(const gt_model* m, void* ctx_, void* arena, floa
       c->e_idx[T] = m->zero_i64; c->e_str[T] = 0; c->e_clamp[T] = -1; tabs[T] = m->vn_emb;
       Tn = T + 1;
     }
-    GT_TRY(gt_embed_sum_fwd(Tn, c->e_idx, c->e_str, c->e_clamp, tabs, N, D, (float*)P(c->o_h[0]), st));
+    // (perturb, when there is one, behind the T node tables and in front of the virtual-node row: the module path's order)
+    GT_TRY(gt_embed_sum_fwd_add(Tn, c->e_idx, c->e_str, c->e_clamp, tabs, b.perturb, T, N, D, (float*)P(c->o_h[0]), st));
     if (k.esort) {   // node ids per table row for the backward: beside the forward, only the index columns are read
       gt_stream_t sst = st;
       if (m->st_dw) {
@@ -1011,6 +1018,9 @@ int Bwd::message_passing() const {
       if (!bc) extra = Q(c->q_dC);
     }
     void* out = dy == Q(c->q_dA) ? Q(c->q_dB) : Q(c->q_dA);
+    // d h_list[0] IS d loss / d perturb: layer 0's input gradient goes straight into the caller's buffer, whichever kernel writes it;
+    // the pooling just below and stage 4 (through c->d_h0) read it from there
+    if (l == 0 && b.d_perturb) out = b.d_perturb;
     if (l == 0 && k.ov) gt_overlap_dw_urgent(1);   // layer 0's weight gradients are the last: nothing left to overlap them with
     const bool pool_on_side = m->has_vn && side;
     void* d_vn = (m->has_vn && !pool_on_side) ? Q(c->q_dvn[3]) : nullptr;

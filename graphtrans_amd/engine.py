@@ -10,7 +10,9 @@ and hands the flat gradient buffer's slices to the parameters.  Autograd sees a 
 Covered configuration (everything else keeps using the module path, see `eligible`):
   GNN_node / GNN_node_Virtualnode with GCNConv or GINConv layers, Linear(<=4, D), BondEncoder-style
   embedding tables or "zero" edge encoders,
-  any gnn_dropout, JK in {last, cat}, ASTNodeEncoder / AtomEncoder / nn.Linear inputs, no perturb;
+  any gnn_dropout, JK in {last, cat}, ASTNodeEncoder / AtomEncoder / nn.Linear inputs; a perturb (FLAG) only on request,
+  `model.fused_flag` (--fused_flag): a contiguous fp32 [N, gnn_emb_dim] tensor, every parameter trainable, no active dist.GradSync
+  -- the forward adds it inside the input encoder, the backward hands d h_list[0] out as its gradient (`_perturb_ok`);
   packed token layout (cls / last pooling, with or without the positional encoder, no masked layers), ReLU / GELU post-norm
   encoder layers; stacked max_seq_len heads or a single head;
   every parameter trainable, or -- on request, `model.fused_freeze` (--fused_freeze) -- exactly `gnn_node` frozen (freeze_gnn /
@@ -94,7 +96,7 @@ class BatchDesc(C.Structure):   # gt_model_batch
                 ("zeros_B", _vp), ("ident_B", _vp), ("ptr01", _vp)] + \
                [(k, _i32) for k in ("training", "compute", "tdt", "will_bwd", "use_w3", "use_w1", "sync_bn", "gnn_frozen")] + \
                [("gnn_p", _f32), ("enc_p", _f32), ("gnn_seed", C.c_uint64), ("enc_seed", C.c_uint64), ("ring", _vp),
-                ("lay_S", _i64), ("lay_meta", _vp)]
+                ("lay_S", _i64), ("lay_meta", _vp), ("perturb", _vp), ("d_perturb", _vp)]
 
 
 class SizesDesc(C.Structure):   # gt_model_sizes
@@ -295,6 +297,7 @@ class _Plan:
         # persistent flat gradient buffer and its per-parameter views
         self.flat = torch.zeros(self.total, dtype=torch.float32, device=self.dev)
         self.views = [self.flat[o:o + p.numel()].view(p.shape) for p, o in self.params]
+        self.flat2 = None   # flat_accum: made by the first accumulating backward of a `fused_flag` model
         self.plist = [p for p, _ in self.params]
         self.param_ptrs = tuple(p.data_ptr() for p in self.plist)
         self.frozen = None   # set_frozen: which parameters the backward hands gradients to
@@ -597,6 +600,13 @@ class _Plan:
         self.tviews = [v for (_, o), v in zip(self.params, self.views) if o >= lo]
         self.trigger = self.tlist[0]   # what the autograd node hangs on: a parameter that requires grad (frozen: gnn2transformer.weight)
 
+    def flat_accum(self):
+        """The second persistent flat gradient buffer (`model.fused_flag`): a backward that accumulates writes it, one add folds it into
+        `flat`.  Zero-filled once: the floats between the parameters' ranges, which no kernel writes, stay zero in both."""
+        if self.flat2 is None:
+            self.flat2 = torch.zeros_like(self.flat)
+        return self.flat2
+
     def _set_min_elems(self):
         self.min_elems = DW_OVERLAP_MIN_ELEMS
         self.cm.dw_overlap_min_elems = DW_OVERLAP_MIN_ELEMS
@@ -686,7 +696,11 @@ def frozen_pattern(model):
 
 def eligible(model, batched_data, perturb):
     """True when the fused path covers this model / call (the static part is cached per model and mode)."""
-    if perturb is not None or not getattr(model, "fused", True):
+    if not getattr(model, "fused", True):
+        return False
+    # a perturbation (FLAG: forward(batched_data, perturb)) sends the model to the module path, unless `model.fused_flag` asks for the
+    # fused step with it (`_perturb_ok`): opt-in, like `fused_freeze`
+    if perturb is not None and not _perturb_ok(model, batched_data, perturb):
         return False
     # the fused node differentiates EVERY parameter and assigns `.grad` itself: any frozen parameter (epoch_callback's freeze_gnn,
     # or a user's requires_grad_(False) on any submodule), any tensor hook on a parameter and a DistributedDataParallel wrapper send
@@ -707,7 +721,10 @@ def eligible(model, batched_data, perturb):
         if w() is not None:
             return False
         st["ddp_wrapper"] = None   # the wrapper is gone
-    key = (model.training, torch.is_grad_enabled(), tuple(flags), bool(getattr(model, "fused_freeze", False)))
+    if perturb is not None and not all(flags):   # (no frozen pattern with a perturbation: the driver rejects perturb + gnn_frozen)
+        return False
+    key = (model.training, torch.is_grad_enabled(), tuple(flags), bool(getattr(model, "fused_freeze", False)),
+           bool(getattr(model, "fused_flag", False)))
     cache = st.setdefault("eligible", {})
     ok = cache.get(key)
     if ok is None:
@@ -749,6 +766,31 @@ def eligible(model, batched_data, perturb):
         if ea is None or ea.dim() != 2 or ea.shape[1] != ee.in_features or not ea.is_cuda or not ea.is_floating_point():
             return False
     return True
+
+
+def emb_dim(model):
+    """gnn_emb_dim: the width of the node rows, and of a perturbation"""
+    gnn = model.gnn_node
+    return int(gnn.layers[0].in_channels if hasattr(gnn, "layers") else gnn.convs[0].emb_dim)
+
+
+def _perturb_ok(model, batched_data, perturb):
+    """what the fused step asks of a call with a perturbation, beside everything it asks without one: the model opted in
+    (`model.fused_flag`, --fused_flag), the perturbation is what the kernels read -- contiguous fp32 [N, gnn_emb_dim] on the device --
+    and no dist.GradSync reduces this model's gradients (FLAG under data parallelism accumulates m backwards before one reduction:
+    the module path)."""
+    if not getattr(model, "fused_flag", False):
+        return False
+    if not (torch.is_tensor(perturb) and perturb.is_cuda and perturb.dtype == torch.float32 and perturb.dim() == 2
+            and perturb.is_contiguous() and perturb.data_ptr() % 16 == 0):
+        return False
+    sync = state(model).get("sync")
+    if sync is not None and sync.active:
+        return False
+    try:
+        return tuple(perturb.shape) == (int(batched_data.batch.numel()), emb_dim(model))
+    except Exception:
+        return False
 
 
 def _grad_flags(params):
@@ -956,7 +998,7 @@ def _num_graphs(batched_data, sizes):
 
 class _FusedModel(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, trigger, model, batched_data, plan):
+    def forward(ctx, trigger, model, batched_data, plan, perturb=None):
         from . import ops
         lib = _lib.lib()
         cm = plan.cm
@@ -1057,6 +1099,15 @@ class _FusedModel(torch.autograd.Function):
         hook = _bn_sync_hook(model, plan) if training else None
         bt.sync_bn = int(hook is not None)
         bt.gnn_frozen = int(plan.frozen)
+        # the perturbation (`eligible` checked it: contiguous fp32 [N, D] on the device).  Its gradient is d h_list[0], which the
+        # backward writes straight into a buffer of ours when somebody will ask for it; otherwise the forward only adds
+        d_perturb = None
+        if perturb is not None:
+            bt.perturb = perturb.data_ptr()
+            keep.append(perturb)
+            if will_bwd and ctx.needs_input_grad[4]:
+                d_perturb = _d_perturb_buffer(N, int(plan.cm.D), plan.dev)
+                bt.d_perturb = d_perturb.data_ptr()
         cbuf = C.create_string_buffer(plan.ctx_bytes)
         sz = SizesDesc()
         if plan.readout:   # no token layout: no staging ring
@@ -1080,7 +1131,7 @@ class _FusedModel(torch.autograd.Function):
                     raise e
         if will_bwd:
             ctx.state = (plan, cbuf, arena, int(sz.barena_bytes), bool(sz.exact), keep, state(model).get("sync"), hook, B,
-                         (plan.frozen, plan.tparams, plan.tlist, plan.tviews))
+                         (plan.frozen, plan.tparams, plan.tlist, plan.tviews), d_perturb, bool(getattr(model, "fused_flag", False)))
         else:
             ctx.state = None
         ctx.set_materialize_grads(False)
@@ -1093,8 +1144,8 @@ class _FusedModel(torch.autograd.Function):
             raise RuntimeError("graphtrans_amd fused model: backward through the graph a second time "
                                "(the saved activations are freed after the first backward)")
         if dlogits is None:
-            return None, None, None, None
-        plan, cbuf, arena, barena_bytes, exact, _keep, model_sync, hook, B, (frozen, tparams, plist, tviews) = s
+            return None, None, None, None, None
+        plan, cbuf, arena, barena_bytes, exact, _keep, model_sync, hook, B, (frozen, tparams, plist, tviews), d_perturb, flag = s
         from . import ops
         lib = _lib.lib()
         dl = dlogits.reshape(B, plan.Nh)
@@ -1109,7 +1160,13 @@ class _FusedModel(torch.autograd.Function):
             if p.grad is not None:
                 direct = False
                 break
-        flat = plan.flat if direct else torch.empty_like(plan.flat)
+        # `model.fused_flag` only: a backward that finds every `.grad` still the plan's own view (FLAG's second and third backward of a
+        # batch) writes a second persistent flat buffer and accumulates with ONE add onto the first; the `.grad` objects stay the views
+        accum = flag and not direct and _grads_are_views(plist, tviews)
+        if accum:
+            flat = plan.flat_accum()
+        else:
+            flat = plan.flat if direct else torch.empty_like(plan.flat)
         barena = (torch.empty if exact else torch.zeros)(barena_bytes, dtype=torch.uint8, device=plan.dev)
         st = _stream()
         args = (plan.cm_ref, cbuf, dl.data_ptr(), flat.data_ptr(), barena.data_ptr())
@@ -1152,15 +1209,35 @@ class _FusedModel(torch.autograd.Function):
         if direct:
             for p, v in zip(plist, tviews):
                 p.grad = v
+        elif accum:
+            lo = plan.ranges[0][0] if frozen else 0   # (frozen: only range 0 was written, only its parameters carry a `.grad`)
+            plan.flat[lo:].add_(flat[lo:])
         else:
             for p, o_ in tparams:
                 v = flat[o_:o_ + p.numel()].view(p.shape)
                 p.grad = v if p.grad is None else p.grad + v
         ctx.state = None
-        return None, None, None, None
+        return None, None, None, None, d_perturb
 
 
-def forward(model, batched_data):
-    """logits (B, Nh) [row-padded storage] of the fused path; `model` must be `eligible`."""
+def _d_perturb_buffer(N, D, dev):
+    """a fresh, uninitialised [N, D] buffer for d perturb: layer 0's input-gradient kernel overwrites every element (a function of its
+    own so a test can hand out a NaN-filled one)"""
+    return torch.empty((N, D), dtype=torch.float32, device=dev)
+
+
+def _grads_are_views(plist, tviews):
+    """every `.grad` is still the view of the plan's flat buffer that an earlier backward handed out (same storage offset, same shape)"""
+    for p, v in zip(plist, tviews):
+        g = p.grad
+        if g is None or g.data_ptr() != v.data_ptr() or g.shape != v.shape or g.dtype != v.dtype or not g.is_contiguous():
+            return False
+    return True
+
+
+def forward(model, batched_data, perturb=None):
+    """logits (B, Nh) [row-padded storage] of the fused path; `model` must be `eligible` (with the same `perturb`)."""
     plan = _plan(model)
-    return _FusedModel.apply(plan.trigger, model, batched_data, plan)
+    if perturb is not None and not torch.is_grad_enabled():
+        perturb = perturb.detach()   # (ctx.needs_input_grad follows requires_grad alone: under no_grad nobody will ask for d perturb)
+    return _FusedModel.apply(plan.trigger, model, batched_data, plan, perturb)

@@ -6,7 +6,7 @@ same ctor `(num_tasks, node_encoder, edge_encoder_cls, args)`, `forward(batched_
     gnn_node -> per-graph read-out (sum | mean | max, ops.graph_pool) -> prediction heads (one GEMM over the stacked weights)
 
 forward() picks between two equivalent data paths:
-  * fused  (engine.eligible: JK = last, every parameter trainable, no perturb, no hooks / DDP wrapper): the whole model as one
+  * fused  (engine.eligible: JK = last, every parameter trainable, no hooks / DDP wrapper; a perturb only with `fused_flag`): the whole model as one
             autograd node on the whole-model driver's read-out mode (csrc/model.hip, gt_model::readout);
   * module path, always available: gnn_node(batched_data, perturb) -> ops.graph_pool -> heads.
 
@@ -49,6 +49,7 @@ class GNN(BaseModel):
         self.num_tasks = num_tasks
         self.max_seq_len = args.max_seq_len
         self.graph_pooling = args.graph_pooling
+        self.fused_flag = bool(getattr(args, "fused_flag", False))   # (engine.eligible: a perturbation on the fused step; no parser flag here)
 
         if self.num_layer < 2:
             raise ValueError("Number of GNN layers must be greater than 1.")
@@ -76,7 +77,7 @@ class GNN(BaseModel):
         if perturb is not None and perturb.shape[0] != batched_data.batch.numel():
             raise ValueError("perturb must have one row per node")
         if engine.eligible(self, batched_data, perturb):   # whole model as one autograd node (engine.py)
-            out = engine.forward(self, batched_data)
+            out = engine.forward(self, batched_data, perturb)
             if self.max_seq_len is None:
                 return out
             return StackedHeads(out.view(out.shape[0], self.max_seq_len, self.num_tasks))

@@ -44,6 +44,8 @@ class GNNTransformer(BaseModel):
         group.add_argument("--freeze_gnn", type=int, default=None, help="Freeze gnn_node weight from epoch `freeze_gnn`")
         group.add_argument("--fused_freeze", default=False, action="store_true",
                            help="keep a model whose gnn_node is frozen (freeze_gnn) on the fused step: its backward stops behind gnn2transformer")
+        group.add_argument("--fused_flag", default=False, action="store_true",
+                           help="keep forward(batched_data, perturb) (the FLAG trainer) on the fused step: it adds perturb and hands out its gradient")
 
     @staticmethod
     def name(args):
@@ -73,6 +75,7 @@ class GNNTransformer(BaseModel):
             self.gnn_node.load_state_dict(self._gnn_node_state(state_dict["model"]))
         self.freeze_gnn = getattr(args, "freeze_gnn", None)
         self.fused_freeze = bool(getattr(args, "fused_freeze", False))
+        self.fused_flag = bool(getattr(args, "fused_flag", False))
 
         gnn_emb_dim = 2 * args.gnn_emb_dim if args.gnn_JK == "cat" else args.gnn_emb_dim
         self.gnn2transformer = nn.Linear(gnn_emb_dim, args.d_model)
@@ -134,7 +137,7 @@ class GNNTransformer(BaseModel):
         enc = self.transformer_encoder
         max_len = int(enc.max_input_len)
         if engine.eligible(self, batched_data, perturb):  # whole model as one autograd node (engine.py)
-            out = engine.forward(self, batched_data)   # graph structure, token layout, forward: one C call (csrc/model.hip)
+            out = engine.forward(self, batched_data, perturb)   # graph structure, token layout, forward: one C call (csrc/model.hip)
             if self.max_seq_len is None:
                 return out
             return StackedHeads(out.view(out.shape[0], self.max_seq_len, self.num_tasks))

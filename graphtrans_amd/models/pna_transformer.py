@@ -29,6 +29,8 @@ class PNATransformer(BaseModel):
         group.add_argument("--freeze_gnn", type=int, default=None, help="Freeze gnn_node weight from epoch `freeze_gnn`")
         group.add_argument("--fused_freeze", default=False, action="store_true",
                            help="keep a model whose gnn_node is frozen (freeze_gnn) on the fused step: its backward stops behind gnn2transformer")
+        group.add_argument("--fused_flag", default=False, action="store_true",
+                           help="keep forward(batched_data, perturb) (the FLAG trainer) on the fused step: it adds perturb and hands out its gradient")
 
     @staticmethod
     def name(args):
@@ -54,6 +56,7 @@ class PNATransformer(BaseModel):
             self.gnn_node.load_state_dict({k.split("gnn_node.", 1)[1]: v for k, v in state_dict.items() if "gnn_node." in k})
         self.freeze_gnn = getattr(args, "freeze_gnn", None)
         self.fused_freeze = bool(getattr(args, "fused_freeze", False))
+        self.fused_flag = bool(getattr(args, "fused_flag", False))
         gnn_emb_dim = 2 * args.gnn_emb_dim if args.gnn_JK == "cat" else args.gnn_emb_dim
         self.gnn2transformer = nn.Linear(gnn_emb_dim, args.d_model)
         self.transformer_encoder = TransformerNodeEncoder(args)
@@ -71,7 +74,7 @@ class PNATransformer(BaseModel):
     def forward(self, batched_data, perturb=None):
         from .. import engine
         if engine.eligible(self, batched_data, perturb):   # whole model as one autograd node, one C call per direction (engine.py)
-            out = engine.forward(self, batched_data)
+            out = engine.forward(self, batched_data, perturb)
             if self.max_seq_len is None:
                 return out
             from .base_model import StackedHeads

@@ -240,6 +240,13 @@ int gt_scale_combine_bwd(const float* grad_out, const float* scales, int64_t num
 int gt_embed_sum_fwd(int num_tables, const int64_t* const* idx_ptrs_host, const int64_t* idx_strides_host,
                      const int64_t* clamp_max_host, const float* const* tables_host, int64_t num_nodes, int64_t dim,
                      float* out, gt_stream_t stream);
+/* ... with one optional fp32 row operand `add` [num_nodes][dim] (16-byte aligned), summed in behind the first `add_before` tables
+ * (0 .. num_tables): out[n] = ((t_0 + .. + t_{add_before-1}) + add[n]) + t_{add_before} + ..., every add in fp32 in that order.  The
+ * FLAG perturbation of forward(batched_data, perturb) (modules/gnn_module.py:158: node tables, then perturb, then -- as one more
+ * stride-0 table -- the virtual-node row).  add == NULL is gt_embed_sum_fwd, bit for bit (the same kernel). */
+int gt_embed_sum_fwd_add(int num_tables, const int64_t* const* idx_ptrs_host, const int64_t* idx_strides_host,
+                         const int64_t* clamp_max_host, const float* const* tables_host, const float* add, int add_before,
+                         int64_t num_nodes, int64_t dim, float* out, gt_stream_t stream);
 size_t gt_embed_sum_bwd_workspace_bytes(int num_tables, const int64_t* table_rows_host, int64_t dim);
 int gt_embed_sum_bwd(int num_tables, const int64_t* const* idx_ptrs_host, const int64_t* idx_strides_host,
                      const int64_t* clamp_max_host, const int64_t* table_rows_host, const float* grad_out,
@@ -1057,6 +1064,14 @@ typedef struct gt_model_batch {
    * on the device (lay_meta = the meta[4] of gt_seq_layout_packed, S = lay_meta[3]) */
   int64_t lay_S;
   const int32_t* lay_meta;
+  /* forward(batched_data, perturb) (FLAG): fp32 [N][D] rows, 16-byte aligned, added to the input encoder's output -- inside
+   * gt_embed_sum_fwd_add behind the node tables and in front of the virtual-node row, or by one gt_add3 behind the Linear node encoder's
+   * GEMM -- or NULL.  Not with gnn_frozen (a frozen stack has no gradient to hand out). */
+  const float* perturb;
+  /* where the backward leaves d loss / d perturb = d h_list[0], fp32 [N][D], 16-byte aligned (needs perturb and will_bwd), or NULL: layer
+   * 0's input-gradient kernel writes there instead of the backward arena (no copy, no extra pass); layer 0's virtual-node pooling and
+   * stage 4 read it from there, so the buffer must stay valid until stage 4 has run.  Overwritten, never accumulated into. */
+  float* d_perturb;
 } gt_model_batch;
 
 typedef struct gt_model_sizes {
@@ -1148,7 +1163,15 @@ int gt_repitch(void* dst, int64_t dst_cols, const void* src, int64_t src_cols, i
                gt_stream_t stream);
 int gt_copy2d(void* dst, int64_t dst_pitch_bytes, const void* src, int64_t src_pitch_bytes, int64_t width_bytes,
               int64_t rows, gt_stream_t stream);
+/* out = a + b (+ c), fp32, n % 4 == 0; out may be a (element i is read before it is written, by the same thread): the whole-model
+ * driver adds a FLAG perturbation to the Linear node encoder's output this way, gt_add3(h0, perturb, NULL, N * D, h0), one launch
+ * behind the GEMM (the table encoders take it inside gt_embed_sum_fwd_add instead) */
 int gt_add3(const float* a, const float* b, const float* c /* or NULL */, int64_t n, float* out, gt_stream_t stream);
+/* FLAG's ascent step (trainers/flag_trainer.py:41-43) in one pass over n elements (n % 4 == 0, else GT_ERR_UNSUPPORTED; 16-byte
+ * aligned, distinct buffers): s = grad > 0 ? 1 : (grad < 0 ? -1 : +0); perturb += step * s; grad = +0.  Equal, bit for bit, to
+ * perturb + step * torch.sign(grad): step * s is exact; a zero gradient of either sign and a NaN gradient give s = +0, as torch.sign
+ * does ((0 < g) - (g < 0)), and leave perturb as it is; +-inf step like any other value. */
+int gt_flag_ascent(float* perturb, float* grad, int64_t n, float step, gt_stream_t stream);
 int gt_rows_gather(int dtype, const void* x, const int64_t* idx, int64_t n, int64_t dim, float* out, gt_stream_t stream);
 /* rows moved in their storage type (the pooled rows of the last encoder layer): take out[i] = x[idx[i]]; put out[idx[i]] = x[i] into
  * a zero-filled [total_rows][dim] matrix; add out[idx[i]] += x[i] (idx must not repeat) */
