@@ -49,6 +49,8 @@ SIGNATURES = {
                               C.POINTER(C.c_int32), _i64, _p, _p, _p, _p, _p, _p, _p, _sz, _p]),
     "gt_pna_aggregate_fwd": (_i, [_p, _p, _i64, _i64, _i, _p, _p, _p, _p, _p, _p, _p]),
     "gt_pna_aggregate_bwd": (_i, [_p, _p, _p, _p, _p, _i64, _i64, _i, _p, _p, _p, _p, _p, _p, _p]),
+    "gt_pna_aggregate_fwd_k": (_i, [_p, _p, _i64, _i64, _i, _i, _p, _p, _p, _p, _p, _p, _p]),
+    "gt_pna_aggregate_bwd_k": (_i, [_p, _p, _p, _p, _p, _i64, _i64, _i, _i, _p, _p, _p, _p, _p, _p, _p]),
     "gt_scale_combine_fwd": (_i, [_p, _p, _i64, _i, _i, _i, _p, _p]),
     "gt_scale_combine_bwd": (_i, [_p, _p, _i64, _i, _i, _i, _p, _p]),
     "gt_embed_sum_fwd": (_i, [_i, _p, _p, _p, _p, _i64, _i64, _p, _p]),
@@ -203,6 +205,8 @@ SIGNATURES = {
     "gt_gather_f32": (_i, [_p, _p, _p, _i64, _p]),
     "gt_pna_aggregate_fwd_uv": (_i, [_p, _p, _i64, _i64, _i, _p, _p, _p, _p, _p, _p, _p]),
     "gt_pna_aggregate_bwd_uv": (_i, [_p, _p, _p, _p, _p, _i64, _i64, _i, _p, _p, _p, _p, _p, _p, _p]),
+    "gt_pna_aggregate_fwd_uv_k": (_i, [_p, _p, _i64, _i64, _i, _i, _p, _p, _p, _p, _p, _p, _p]),
+    "gt_pna_aggregate_bwd_uv_k": (_i, [_p, _p, _p, _p, _p, _i64, _i64, _i, _i, _p, _p, _p, _p, _p, _p, _p]),
     "gt_rows_take": (_i, [_i, _p, _p, _i64, _i64, _p, _p]),
     "gt_rows_put": (_i, [_i, _p, _p, _i64, _i64, _i64, _p, _p]),
     "gt_rows_add": (_i, [_i, _p, _p, _i64, _i64, _p, _p]),

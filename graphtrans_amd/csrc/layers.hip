@@ -755,8 +755,10 @@ extern "C" int gt_encoder_layer_pooled_bwd(const gt_encoder_layer* L, const void
 // =================================================================================================
 // PNA layer (modules/pna/pna_module.py:57-78; PNAConv math: modules/pna_layer.py:131-167)
 namespace {
+// K = the aggregate kernel's slot count (gt_pna_layer::agg_slots: a zeroed field is the classic 4); the post-Linear's operand is (1 + K) F wide
+inline int pna_slots(const gt_pna_layer* L) { return L->agg_slots ? L->agg_slots : 4; }
 struct PnaSaved {
-  float *UV, *in5, *mean_v, *out, *z, *stats;
+  float *UV, *opnd, *mean_v, *out, *z, *stats;
   int32_t* arg;
   size_t bytes;
 };
@@ -765,7 +767,7 @@ PnaSaved pna_saved(const gt_pna_layer* L, void* p) {
   PnaSaved s;
   const size_t ND = (size_t)L->N * L->D;
   s.UV = (float*)b.take(ND * 2 * 4);
-  s.in5 = (float*)b.take(ND * 5 * 4);
+  s.opnd = (float*)b.take(ND * (1 + pna_slots(L)) * 4);
   s.mean_v = (float*)b.take(ND * 4);
   s.arg = (int32_t*)b.take(ND * 2 * 4);
   s.out = (float*)b.take(ND * 4);
@@ -775,7 +777,7 @@ PnaSaved pna_saved(const gt_pna_layer* L, void* p) {
   return s;
 }
 struct PnaWork {
-  float *Y, *g, *d_z, *d_out, *d_in5, *dUV, *dxpart;
+  float *Y, *g, *d_z, *d_out, *d_opnd, *dUV, *dxpart;
   void *bn_ws, *lin_ws, *post_ws, *pre_ws;   // one GEMM workspace each: a forked weight-gradient GEMM still uses its own while the next runs
   size_t bn_ws_bytes, lin_ws_bytes, post_ws_bytes, pre_ws_bytes, bytes;
 };
@@ -788,14 +790,14 @@ PnaWork pna_work(const gt_pna_layer* L, void* p) {
   w.g = (float*)b.take(ND * 4);
   w.d_z = (float*)b.take(ND * 4);
   w.d_out = (float*)b.take(ND * 4);
-  w.d_in5 = (float*)b.take(ND * 5 * 4);
+  w.d_opnd = (float*)b.take(ND * (1 + pna_slots(L)) * 4);
   w.dUV = (float*)b.take(ND * 2 * 4);
   w.dxpart = (float*)b.take(ND * 4);
   w.bn_ws_bytes = gt_batchnorm_workspace_bytes(L->N, L->D);
   w.bn_ws = b.take(w.bn_ws_bytes);
   w.lin_ws_bytes = gt_linear_bwd_workspace_bytes(L->compute, L->N, L->D, L->D);
   w.lin_ws = b.take(w.lin_ws_bytes);
-  w.post_ws_bytes = gt_linear_bwd_grouped_workspace_bytes(L->compute, L->N, L->S * F, 5 * F, L->T);
+  w.post_ws_bytes = gt_linear_bwd_grouped_workspace_bytes(L->compute, L->N, L->S * F, (1 + pna_slots(L)) * F, L->T);
   w.post_ws = b.take(w.post_ws_bytes);
   w.pre_ws_bytes = gt_linear_bwd_grouped_workspace_bytes(L->compute, L->N, 2 * F, F, L->T);
   w.pre_ws = b.take(w.pre_ws_bytes);
@@ -804,6 +806,10 @@ PnaWork pna_work(const gt_pna_layer* L, void* p) {
 }
 int pna_layer_check(const char* fn, const gt_pna_layer* L) {
   if (!L) { gt_set_error("%s: null descriptor", fn); return GT_ERR_INVALID_ARG; }
+  if (L->agg_slots != 0 && L->agg_slots != 4 && L->agg_slots != 6) {
+    gt_set_error("%s: agg_slots must be 0 or 4 ([mean | max | min | std]) or 6 (+ [sum | var])", fn);
+    return GT_ERR_INVALID_ARG;
+  }
   if (L->N < 0 || L->D <= 0 || L->T <= 0 || L->D % L->T || (L->D / L->T) % 4 || L->D > 1024 || L->S < 1 || L->S > 8) {
     gt_set_error("%s: bad sizes (need D %% T == 0, (D / T) %% 4 == 0, D <= 1024, 1 <= S <= 8)", fn);
     return GT_ERR_INVALID_ARG;
@@ -829,12 +835,13 @@ extern "C" int gt_pna_layer_fwd(const gt_pna_layer* L, const void* x, void* y, v
   if (L->N == 0) return GT_OK;
   const PnaSaved s = pna_saved(L, saved);
   const int64_t N = L->N, D = L->D, F = D / L->T;
-  const int T = L->T, S = L->S;
+  const int T = L->T, S = L->S, K = pna_slots(L);
+  const int64_t KF = (1 + K) * F;   // the post-Linear's operand width per tower: [x | K aggregates]
   // [U_t | V_t] = x_t [A_t ; B_t]^T + [b_t | 0]: the per-edge Linear(2F, F) split into its target-role and source-role halves
   GT_TRY(gt_linear_fwd_grouped(GT_F32, GT_F32, L->compute, x, L->pre_w, L->pre_b, s.UV, N, 2 * F, F, D, 2 * D, T, F, 2 * F, 0, 0.f, 0, st));
-  GT_TRY(gt_pna_aggregate_fwd_uv(s.UV, (const float*)x, N, D, T, L->in_ptr, L->in_src, L->in_eid, s.in5, s.mean_v, s.arg, st));
+  GT_TRY(gt_pna_aggregate_fwd_uv_k(s.UV, (const float*)x, N, D, T, K, L->in_ptr, L->in_src, L->in_eid, s.opnd, s.mean_v, s.arg, st));
   // the post-Linear once on [x | agg]; its S per-scaler output blocks are combined with the degree scalers
-  GT_TRY(gt_linear_fwd_grouped(GT_F32, GT_F32, L->compute, s.in5, L->post_w, L->post_b, w.Y, N, S * F, 5 * F, 5 * D, S * D, T, 5 * F, S * F, 0,
+  GT_TRY(gt_linear_fwd_grouped(GT_F32, GT_F32, L->compute, s.opnd, L->post_w, L->post_b, w.Y, N, S * F, KF, T * KF, S * D, T, KF, S * F, 0,
                                0.f, 0, st));
   GT_TRY(gt_scale_combine_fwd(w.Y, L->scales, N, T, S, (int)F, s.out, st));
   GT_TRY(gt_linear_fwd(GT_F32, GT_F32, L->compute, s.out, L->lin_w, L->lin_b, s.z, N, D, D, 0, 0.f, 0, st));
@@ -855,7 +862,8 @@ extern "C" int gt_pna_layer_bwd(const gt_pna_layer* L, const void* x, const void
   if (L->N == 0) return GT_OK;
   const PnaSaved s = pna_saved(L, const_cast<void*>(saved));
   const int64_t N = L->N, D = L->D, F = D / L->T;
-  const int T = L->T, S = L->S;
+  const int T = L->T, S = L->S, K = pna_slots(L);
+  const int64_t KF = (1 + K) * F;
   float *g_lin_w = grads, *g_lin_b = grads + D * D, *g_bn_w = g_lin_b + D, *g_bn_b = g_bn_w + D;
   const void* g = dy;
   if (L->training && L->dropout_p > 0.f) {   // the mask is a function of (element, seed): the same call on the gradient
@@ -867,9 +875,9 @@ extern "C" int gt_pna_layer_bwd(const gt_pna_layer* L, const void* x, const void
   GT_TRY(gt_linear_bwd(GT_F32, GT_F32, L->compute, s.out, L->lin_w, w.d_z, nullptr, nullptr, nullptr, w.d_out, g_lin_w, g_lin_b, N, D, D, 0.f,
                        w.lin_ws, w.lin_ws_bytes, st));
   GT_TRY(gt_scale_combine_bwd(w.d_out, L->scales, N, T, S, (int)F, w.Y, st));
-  GT_TRY(gt_linear_bwd_grouped(GT_F32, GT_F32, L->compute, s.in5, L->post_w, w.Y, nullptr, nullptr, nullptr, w.d_in5, L->d_post_w, L->d_post_b,
-                               N, S * F, 5 * F, 5 * D, S * D, T, 5 * F, S * F, 0.f, w.post_ws, w.post_ws_bytes, st));
-  GT_TRY(gt_pna_aggregate_bwd_uv(s.UV, s.in5, s.mean_v, s.arg, w.d_in5, N, D, T, L->in_ptr, L->out_ptr, L->out_dst, L->out_eid, w.dUV,
+  GT_TRY(gt_linear_bwd_grouped(GT_F32, GT_F32, L->compute, s.opnd, L->post_w, w.Y, nullptr, nullptr, nullptr, w.d_opnd, L->d_post_w, L->d_post_b,
+                               N, S * F, KF, T * KF, S * D, T, KF, S * F, 0.f, w.post_ws, w.post_ws_bytes, st));
+  GT_TRY(gt_pna_aggregate_bwd_uv_k(s.UV, s.opnd, s.mean_v, s.arg, w.d_opnd, N, D, T, K, L->in_ptr, L->out_ptr, L->out_dst, L->out_eid, w.dUV,
                                  w.dxpart, st));
   // dx = dUV [A ; B] + (the x block of the post-Linear's operand) + (the residual branch)
   GT_TRY(gt_linear_bwd_grouped(GT_F32, GT_F32, L->compute, x, L->pre_w, w.dUV, nullptr, w.dxpart, g, dx, L->d_pre_w, L->d_pre_b, N, 2 * F, F, D,

@@ -487,6 +487,8 @@ class _Plan:
         A, S = len(c0.aggregators), len(c0._blocks)
         first = S - len(c0.scalers)
         cols = (A * len(c0.scalers) + 1) * F
+        K = c0.agg_slots          # the aggregate kernel's slot count: 4, or 6 with sum / var
+        KF = (1 + K) * F          # the post-Linear's operand [x | K aggregates] per tower
         self.conv_desc = (layers.PnaLayerDesc * L)()
         # ---- flat tower storage: per layer [pre_w (T,F,2F) | pre_b (T,F) | post_w (T,F,cols) | post_b (T,F)]
         per_layer = T * F * 2 * F + T * F + T * F * cols + T * F
@@ -497,8 +499,8 @@ class _Plan:
         assert flat.numel() == n_src and tuple(towers[0].shape) == (F, 2 * F) and tuple(towers[2 * T].shape) == (F, cols)
         tower_params = list(zip(towers, offs))   # (param, offset inside the flat storage)
         self.pna_flat = flat
-        # ---- image layout per layer: [pre_stack (T,2F,F) | pre_b2 (T,2F) | Wst (T,S*F,5F) | bst (T,S*F)] and the gather map
-        img_per_layer = T * 2 * F * F + T * 2 * F + T * S * F * 5 * F + T * S * F
+        # ---- image layout per layer: [pre_stack (T,2F,F) | pre_b2 (T,2F) | Wst (T,S*F,(1+K)F) | bst (T,S*F)] and the gather map
+        img_per_layer = T * 2 * F * F + T * 2 * F + T * S * F * KF + T * S * F
         n_img = L * img_per_layer
         mp = np.full(n_img, -1, dtype=np.int64)
         t_ = np.arange(T).reshape(T, 1, 1)
@@ -508,7 +510,7 @@ class _Plan:
             s_post_w, s_post_b = s_pre_b + T * F, s_pre_b + T * F + T * F * cols
             ib = l * img_per_layer
             i_pre_w, i_pre_b = ib, ib + T * 2 * F * F
-            i_post_w, i_post_b = i_pre_b + T * 2 * F, i_pre_b + T * 2 * F + T * S * F * 5 * F
+            i_post_w, i_post_b = i_pre_b + T * 2 * F, i_pre_b + T * 2 * F + T * S * F * KF
             r = np.arange(2 * F).reshape(1, 2 * F, 1)
             k = np.arange(F).reshape(1, 1, F)
             src = s_pre_w + t_ * (F * 2 * F) + np.where(r < F, r, r - F) * (2 * F) + np.where(r < F, 0, F) + k
@@ -516,8 +518,8 @@ class _Plan:
             rb = np.arange(2 * F).reshape(1, 2 * F)
             srcb = np.where(rb < F, s_pre_b + np.arange(T).reshape(T, 1) * F + rb, -1)
             mp[i_pre_b:i_pre_b + T * 2 * F] = srcb.reshape(-1)
-            # post: block s of tower t, output o, operand column c in [x | mean | max | min | std] (modules/pna/pna_module.py:_post_maps)
-            w = np.full((T, S * F, 5 * F), -1, dtype=np.int64)
+            # post: block s of tower t, output o, operand column c in [x | mean | max | min | std (| sum | var)] (modules/pna/pna_module.py:_post_maps)
+            w = np.full((T, S * F, KF), -1, dtype=np.int64)
             o = np.arange(F).reshape(F, 1)
             f = np.arange(F).reshape(1, F)
             for t in range(T):
@@ -531,7 +533,7 @@ class _Plan:
                     for ai, a in enumerate(c0.aggregators):
                         slot = _AGG_SLOT[a]
                         w[t, rows, F + slot * F:F + (slot + 1) * F] = tb + o * cols + F + (s_ - first) * A * F + ai * F + f
-            mp[i_post_w:i_post_w + T * S * F * 5 * F] = w.reshape(-1)
+            mp[i_post_w:i_post_w + T * S * F * KF] = w.reshape(-1)
             bb = np.full((T, S * F), -1, dtype=np.int64)
             bb[:, :F] = s_post_b + np.arange(T).reshape(T, 1) * F + np.arange(F).reshape(1, F)
             mp[i_post_b:i_post_b + T * S * F] = bb.reshape(-1)
@@ -550,6 +552,7 @@ class _Plan:
             self.w3_weights.append(conv.lin.weight)
             desc = self.conv_desc[l]
             desc.D, desc.T, desc.S = D, T, S
+            desc.agg_slots = K
             ib = l * img_per_layer
             base = self.pna_img.data_ptr()
             desc.pre_w, desc.pre_b = base + 4 * cm.pna_img_off[l][0], base + 4 * cm.pna_img_off[l][1]
@@ -562,7 +565,7 @@ class _Plan:
         self.pna_tower_views = []
         if PNA_TOWER_IMAGES:
             for l in range(L):
-                for j, (rows_, cols_) in ((0, (2 * F, F)), (2, (S * F, 5 * F))):
+                for j, (rows_, cols_) in ((0, (2 * F, F)), (2, (S * F, KF))):
                     o0 = int(cm.pna_img_off[l][j])
                     for t in range(T):
                         v = self.pna_img[o0 + t * rows_ * cols_:o0 + (t + 1) * rows_ * cols_].view(rows_, cols_)

@@ -71,7 +71,7 @@ class PnaLayerDesc(C.Structure):   # gt_pna_layer
                [(n, _fp) for n in ("in_ptr", "in_src", "in_eid", "out_ptr", "out_dst", "out_eid", "scales", "pre_w", "pre_b", "post_w",
                                    "post_b", "lin_w", "lin_b", "bn_w", "bn_b", "bn_rm", "bn_rv", "bn_nbt", "d_pre_w", "d_pre_b",
                                    "d_post_w", "d_post_b")] + \
-               [("seed", C.c_uint64), ("dropout_p", C.c_float), ("pad_", C.c_int32)]
+               [("seed", C.c_uint64), ("dropout_p", C.c_float), ("agg_slots", C.c_int32)]   # agg_slots: 0 / 4 classic, 6 with sum / var
 
 
 def _any_sync(*bns):

@@ -7,9 +7,9 @@ modules/pna/{aggregators,scalers}.py.  Parameter names / state_dict keys follow 
 and `batch_norms.{i}.module.*` (PyG's BatchNorm wraps nn.BatchNorm1d as `.module`).
 
 Data path: the per-edge pre-Linear is split into per-node terms (U = x A^T + b for the target role,
-V = x B^T for the source role; two small batched GEMMs), the four aggregators run in ONE HIP pass
-over the CSR (gt_pna_aggregate_fwd/bwd), the degree scalers are per-node scalars applied while the
-post-Linear input is assembled.
+V = x B^T for the source role; two small batched GEMMs), the aggregators run in ONE HIP pass over the
+CSR (gt_pna_aggregate_fwd/bwd: K = 4 slots [mean|max|min|std], or K = 6 with [sum|var] once a layer
+names either), the degree scalers are per-node scalars applied while the post-Linear input is assembled.
 """
 import math
 
@@ -20,7 +20,12 @@ from ... import ops
 from ..gnn_module import batch_structure
 from ..norm import BatchNorm1d
 
-_AGG_SLOT = {"mean": 0, "max": 1, "min": 2, "std": 3}
+_AGG_SLOT = {"mean": 0, "max": 1, "min": 2, "std": 3, "sum": 4, "var": 5}
+
+
+def agg_slots(aggregators):
+    """The kernel's slot count K for a list of aggregator names: 4 = [mean|max|min|std], 6 as soon as sum or var appears."""
+    return 6 if any(_AGG_SLOT[a] >= 4 for a in aggregators) else 4
 
 
 class _Restack(torch.autograd.Function):
@@ -53,6 +58,7 @@ class PNAConv(nn.Module):
         self.in_channels, self.out_channels = in_channels, out_channels
         self.aggregators, self.scalers = list(aggregators), list(scalers)
         self.towers, self.divide_input = towers, divide_input
+        self.agg_slots = agg_slots(self.aggregators)
         self.F_in = in_channels // towers if divide_input else in_channels
         self.F_out = out_channels // towers
         # the kernels move 16-byte chunks of a tower's row: per-tower widths that are not multiples of 4 (the reference's default
@@ -95,16 +101,16 @@ class PNAConv(nn.Module):
         return out
 
     def _post_maps(self, device):
-        """Gather maps that restack post_nns[t].weight (F_out, (A*S+1)F) into (S*F_out, 5F): block s holds the
-        columns of scaler s over the kernel's [mean|max|min|std] slots (zeros for unused aggregators) and, for s = 0
-        only, the x_i columns.  Then  post(cat[x, agg*s_0, agg*s_1, ...]) = sum_s scale_s (x) Y[:, s]."""
+        """Gather maps that restack post_nns[t].weight (F_out, (A*S+1)F) into (S*F_out, (1+K)F): block s holds the
+        columns of scaler s over the kernel's K slots [mean|max|min|std] or [mean|max|min|std|sum|var] (zeros for
+        unused aggregators) and, for s = 0 only, the x_i columns.  Then  post(cat[x, agg*s_0, agg*s_1, ...]) = sum_s scale_s (x) Y[:, s]."""
         key = str(device)
         if getattr(self, "_maps_key", None) == key:
             return self._wmap, self._bmap
         Fi, Fo, A, S = self.F_in, self.F_out, len(self.aggregators), len(self._blocks)
         cols = (A * len(self.scalers) + 1) * Fi
         zero_w = Fo * cols   # index of the appended zero
-        wmap = torch.full((S * Fo, 5 * Fi), zero_w, dtype=torch.int64)
+        wmap = torch.full((S * Fo, (1 + self.agg_slots) * Fi), zero_w, dtype=torch.int64)
         o = torch.arange(Fo).view(Fo, 1)
         f = torch.arange(Fi).view(1, Fi)
         first = S - len(self.scalers)   # 1 when block 0 only carries x_i and the bias
@@ -138,7 +144,7 @@ class PNAConv(nn.Module):
             from ...graph import GraphStructure
             gs = GraphStructure.build(edge_index, torch.zeros(x.shape[0], dtype=torch.int64, device=x.device), num_graphs=1)
         N, T, Fi, Fo = x.shape[0], self.towers, self.F_in, self.F_out
-        S = len(self._blocks)
+        S, K = len(self._blocks), self.agg_slots
         if Fi % 4:
             return self._forward_padded(x, gs)
         xt = (x.view(N, T, Fi) if self.divide_input else x.view(N, 1, Fi).expand(N, T, Fi)).contiguous()
@@ -147,15 +153,15 @@ class PNAConv(nn.Module):
         # the per-edge pre-Linear splits into per-node terms: U = x A^T + b (target role), V = x B^T (source role)
         U = ops.tower_linear(xt, Wp[:, :, :Fi].contiguous(), bp).view(N, T * Fi)
         V = ops.tower_linear(xt, Wp[:, :, Fi:].contiguous(), None).view(N, T * Fi)
-        agg4 = ops.pna_aggregate(U, V, gs, T).view(N, T, 4 * Fi)         # [mean | max | min | std]
+        agg = ops.pna_aggregate(U, V, gs, T, K).view(N, T, K * Fi)       # [mean | max | min | std (| sum | var)]
         # post-Linear without materialising the (A*S+1)F-wide scaled copies: one GEMM on [x | agg] per tower,
         # the degree scalers (per-node scalars) are applied to its S output blocks
         wmap, bmap = self._post_maps(x.device)
         Wq = torch.stack([m[0].weight for m in self.post_nns])           # (T, F_out, (A*S+1)F)
         bq = torch.stack([m[0].bias for m in self.post_nns])             # (T, F_out)
-        Wst = _Restack.apply(Wq.reshape(T, -1), wmap, self._winv).view(T, S * Fo, 5 * Fi)
+        Wst = _Restack.apply(Wq.reshape(T, -1), wmap, self._winv).view(T, S * Fo, (1 + K) * Fi)
         bst = _Restack.apply(bq, bmap, self._binv)
-        Y = ops.tower_linear(torch.cat([xt, agg4], dim=-1), Wst, bst).view(N, T, S, Fo)
+        Y = ops.tower_linear(torch.cat([xt, agg], dim=-1), Wst, bst).view(N, T, S, Fo)
         # the degree scalers depend on the batch's graph structure only: computed by the first layer, reused by the rest
         cache = getattr(gs, "_pna_scales", None)
         key = (tuple(self._blocks), self.avg_deg["log"], self.avg_deg["lin"])
@@ -174,7 +180,7 @@ class PNAConv(nn.Module):
     def _forward_padded(self, x, gs):
         """Per-tower width F not a multiple of 4 (F = 75 for the reference's default gnn_emb_dim 300 with 4 towers): every tower row is
         zero-padded to Fp = ceil4(F) -- inputs, the pre-Linear's weight blocks and bias, the post-Linear's operand columns and
-        output rows.  Padded columns carry U = V = 0, so their aggregates are 0 / 0 / 0 / sqrt(1e-5) and meet zero weight columns in
+        output rows.  Padded columns carry U = V = 0, so their aggregates are 0 / 0 / 0 / sqrt(1e-5) (/ 0 / 0) and meet zero weight columns in
         the post-Linear; padded outputs are cut off before `lin`.  Same kernels as the aligned path on (N, T, Fp) operands; torch's
         pad / slice ops and their autograd do the re-layout (this configuration is not on the fused path)."""
         import torch.nn.functional as Fn
@@ -189,7 +195,8 @@ class PNAConv(nn.Module):
         Wb = Fn.pad(Wp[:, :, F:], (0, pad, 0, pad)).contiguous()
         U = ops.tower_linear(xt, Wa, bp).view(N, T * Fp)
         V = ops.tower_linear(xt, Wb, None).view(N, T * Fp)
-        agg = ops.pna_aggregate(U, V, gs, T).view(N, T, 4, Fp)                         # kernel slots [mean | max | min | std]
+        K = self.agg_slots
+        agg = ops.pna_aggregate(U, V, gs, T, K).view(N, T, K, Fp)                      # kernel slots [mean | max | min | std (| sum | var)]
         sel = agg[:, :, [_AGG_SLOT[a] for a in self.aggregators], :]                   # (N, T, A, Fp) in the module's aggregator order
         deg = (gs.in_ptr[1:] - gs.in_ptr[:-1]).to(torch.float32).view(-1, 1, 1, 1)
         scs = []

@@ -782,16 +782,22 @@ def linear_module(mod, x, act=None, dropout_p=0.0, seed=0):
 # ------------------------------------------------------------------------------------------------
 class _PnaAggregate(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, U, V, gs, towers):
+    def forward(ctx, U, V, gs, towers, slots):
+        if slots not in (4, 6):
+            raise ValueError(f"pna_aggregate: slots must be 4 or 6, got {slots}")
         U, V = _dev(U.float(), "U"), _dev(V.float(), "V")
         N, D = V.shape
-        out = torch.empty((N, towers, 4 * (D // towers)), dtype=torch.float32, device=V.device)
+        out = torch.empty((N, towers, slots * (D // towers)), dtype=torch.float32, device=V.device)
         mean_v = torch.empty_like(V)
         arg = torch.empty((N, 2, D), dtype=torch.int32, device=V.device)
-        _lib.launch("gt_pna_aggregate_fwd", _ptr(U), _ptr(V), N, D, towers, _ptr(gs.in_ptr), _ptr(gs.in_src),
-                    _ptr(gs.in_eid), _ptr(out), _ptr(mean_v), _ptr(arg), _stream())
+        if slots == 4:
+            _lib.launch("gt_pna_aggregate_fwd", _ptr(U), _ptr(V), N, D, towers, _ptr(gs.in_ptr), _ptr(gs.in_src),
+                        _ptr(gs.in_eid), _ptr(out), _ptr(mean_v), _ptr(arg), _stream())
+        else:
+            _lib.launch("gt_pna_aggregate_fwd_k", _ptr(U), _ptr(V), N, D, towers, slots, _ptr(gs.in_ptr), _ptr(gs.in_src),
+                        _ptr(gs.in_eid), _ptr(out), _ptr(mean_v), _ptr(arg), _stream())
         ctx.save_for_backward(V, out, mean_v, arg)
-        ctx.gs, ctx.towers = gs, towers
+        ctx.gs, ctx.towers, ctx.slots = gs, towers, slots
         return out
 
     @staticmethod
@@ -801,14 +807,19 @@ class _PnaAggregate(torch.autograd.Function):
         g = _dev(g.float(), "grad")
         N, D = V.shape
         dU, dV = torch.empty_like(V), torch.empty_like(V)
-        _lib.launch("gt_pna_aggregate_bwd", _ptr(V), _ptr(out), _ptr(mean_v), _ptr(arg), _ptr(g), N, D, ctx.towers,
-                    _ptr(gs.in_ptr), _ptr(gs.out_ptr), _ptr(gs.out_dst), _ptr(gs.out_eid), _ptr(dU), _ptr(dV), _stream())
-        return dU, dV, None, None
+        if ctx.slots == 4:
+            _lib.launch("gt_pna_aggregate_bwd", _ptr(V), _ptr(out), _ptr(mean_v), _ptr(arg), _ptr(g), N, D, ctx.towers,
+                        _ptr(gs.in_ptr), _ptr(gs.out_ptr), _ptr(gs.out_dst), _ptr(gs.out_eid), _ptr(dU), _ptr(dV), _stream())
+        else:
+            _lib.launch("gt_pna_aggregate_bwd_k", _ptr(V), _ptr(out), _ptr(mean_v), _ptr(arg), _ptr(g), N, D, ctx.towers, ctx.slots,
+                        _ptr(gs.in_ptr), _ptr(gs.out_ptr), _ptr(gs.out_dst), _ptr(gs.out_eid), _ptr(dU), _ptr(dV), _stream())
+        return dU, dV, None, None, None
 
 
-def pna_aggregate(U, V, gs, towers):
-    """(N, towers, 4F): [U+mean V | U+max V | U+min V | std V] over the in-edges (gt_pna_aggregate_*)."""
-    return _PnaAggregate.apply(U, V, gs, towers)
+def pna_aggregate(U, V, gs, towers, slots=4):
+    """(N, towers, slots * F) over the in-edges (gt_pna_aggregate_*): [U+mean V | U+max V | U+min V | std V] for slots = 4,
+    followed by [deg U + sum V | var V] for slots = 6."""
+    return _PnaAggregate.apply(U, V, gs, towers, slots)
 
 
 EMBED_SORT_MAX_ROWS = 16384   # gt_embed_sort's per-block LDS histogram

@@ -204,8 +204,8 @@ int gt_aggregate_bwd(int conv, int edge_mode, int dtype, const void* h, const vo
                      size_t workspace_bytes, gt_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------------
- * PNA multi-aggregator message passing (mean | max | min | std over the in-edges in one pass).
- * Replaces PyG PNAConv's per-edge Linear + 4 torch_scatter reductions (modules/pna/pna_module.py:73;
+ * PNA multi-aggregator message passing (mean | max | min | std, with the _k entries also | sum | var, over the in-edges in one pass).
+ * Replaces PyG PNAConv's per-edge Linear + its torch_scatter reductions, one per aggregator (modules/pna/pna_module.py:73;
  * math stated in-tree by modules/pna_layer.py:131-167, modules/pna/aggregators.py:11-34).  The
  * per-edge message pre_nn_t([x_i || x_j]) is split into per-node terms m_k = U[i] + V[j_k]
  * (U = x A_t^T + b, V = x B_t^T computed by the caller):
@@ -222,6 +222,20 @@ int gt_pna_aggregate_bwd(const float* V, const float* out, const float* mean_v, 
                          const float* grad_out, int64_t num_nodes, int64_t dim, int towers, const int32_t* in_ptr,
                          const int32_t* out_ptr, const int32_t* out_dst, const int32_t* out_eid, float* dU, float* dV,
                          gt_stream_t stream);
+/* The same pass with `slots` = K aggregator slots per tower, out / grad_out [N][towers][K F]:
+ *   K = 4: [mean | max | min | std], the two entries above (same kernels, same bits);
+ *   K = 6: [mean | max | min | std | sum | var] with the reference's other two aggregators (modules/pna/aggregators.py:11-34):
+ *     sum = deg U + sum_k V[j_k];   var = E[m^2] - E[m]^2 without relu or epsilon, computed shift-free as the Welford M2 / deg (never
+ *     negative; exactly 0 for in-degree <= 1);   empty neighbourhood: 0, 0.
+ *     Backward: dV[j] += g_sum[i] + g_var[i] * 2 (V[j] - mean_v[i]) / deg_i per edge j -> i;   dU[i] += deg_i g_sum[i].
+ * Any other K returns GT_ERR_INVALID_ARG.  mean_v and arg are as above (no further saved tensor). */
+int gt_pna_aggregate_fwd_k(const float* U, const float* V, int64_t num_nodes, int64_t dim, int towers, int slots,
+                           const int32_t* in_ptr, const int32_t* in_src, const int32_t* in_eid, float* out,
+                           float* mean_v, int32_t* arg, gt_stream_t stream);
+int gt_pna_aggregate_bwd_k(const float* V, const float* out, const float* mean_v, const int32_t* arg,
+                           const float* grad_out, int64_t num_nodes, int64_t dim, int towers, int slots, const int32_t* in_ptr,
+                           const int32_t* out_ptr, const int32_t* out_dst, const int32_t* out_eid, float* dU, float* dV,
+                           gt_stream_t stream);
 /* Degree scalers of PNAConv (modules/pna/scalers.py:10-31) applied to the S per-scaler output blocks of the
  * post-Linear: out[n][t][f] = sum_s Y[n][t][s][f] * scales[n][s]; bwd: dY = grad_out (x) scales (scales: no grad). */
 int gt_scale_combine_fwd(const float* Y, const float* scales, int64_t num_nodes, int towers, int num_scalers, int F,
@@ -898,9 +912,11 @@ const float* gt_vn_update_bwd_dt0(const gt_vn_update* L, void* workspace);
  * on re-stacked IMAGES of the tower weights (built by the caller with gt_gather_f32 once per step, all layers in one launch):
  *   pre_w  [T][2F][F] = [A_t ; B_t] (pre_nns[t].weight [F][2F] = [A_t | B_t]: U = x_t A_t^T + b_t is the target-role term, V = x_t B_t^T the
  *                       source-role term of the per-edge Linear), pre_b [T][2F] = [b_t | 0]
- *   post_w [T][S Fo][5F]: block s = the columns of scaler s over the kernel's [x | mean | max | min | std] operand (x and the bias in
- *                       block 0 only, zeros for unused aggregators), post_b [T][S Fo]; scales [N][S] = the per-node degree scalers.
- * One grouped GEMM gives [U | V] for all towers, the aggregate kernel writes [x | mean | max | min | std] where the grouped post-GEMM
+ *   post_w [T][S Fo][(1+K) F]: block s = the columns of scaler s over the kernel's [x | mean | max | min | std (| sum | var)] operand (x and
+ *                       the bias in block 0 only, zeros for unused aggregators), post_b [T][S Fo]; scales [N][S] = the per-node degree
+ *                       scalers.  K = agg_slots: 0 or 4 = [mean | max | min | std] (a zeroed field keeps the classic layout), 6 =
+ *                       [mean | max | min | std | sum | var]; anything else returns GT_ERR_INVALID_ARG.
+ * One grouped GEMM gives [U | V] for all towers, the aggregate kernel writes [x | aggregates] where the grouped post-GEMM
  * reads it, its S output blocks are combined with the scalers, then lin + BatchNorm + ReLU + residual.  `grads` (gradient order):
  * lin_w [D][D], lin_b [D], bn_w [D], bn_b [D]; the image gradients go to d_pre_w / d_pre_b / d_post_w / d_post_b (same shapes as the
  * images; the caller maps them back onto the parameters with gt_gather_f32 through the inverse map). */
@@ -917,7 +933,7 @@ typedef struct gt_pna_layer {
   float *d_pre_w, *d_pre_b, *d_post_w, *d_post_b; /* image gradients (backward) */
   uint64_t seed;
   float dropout_p;
-  int32_t pad_;
+  int32_t agg_slots;   /* K: 0 or 4 classic, 6 with sum and var */
 } gt_pna_layer;
 size_t gt_pna_layer_saved_bytes(const gt_pna_layer* layer);
 size_t gt_pna_layer_workspace_bytes(const gt_pna_layer* layer);
@@ -933,7 +949,7 @@ int gt_pna_scales(const int32_t* in_ptr, int64_t num_nodes, int num_scalers, con
                   float* scales, gt_stream_t stream);
 /* dst[i] = map[i] < 0 ? 0 : src[map[i]] (fp32): re-stacked weight images and, through the inverse map, their gradients */
 int gt_gather_f32(float* dst, const float* src, const int32_t* map, int64_t n, gt_stream_t stream);
-/* gt_pna_aggregate_* on the fused layer's layouts: UV [N][T][2F] = [U_t | V_t], in5 [N][T][5F] = [x_t | mean | max | min | std]
+/* gt_pna_aggregate_* on the fused layer's layouts: UV [N][T][2F] = [U_t | V_t], the K = 4 operand in5 [N][T][5F] = [x_t | mean | max | min | std]
  * (x copied on the way in), backward from d_in5 to dUV [N][T][2F] and the x block's gradient dxpart [N][D]. */
 int gt_pna_aggregate_fwd_uv(const float* UV, const float* x, int64_t num_nodes, int64_t dim, int towers, const int32_t* in_ptr,
                             const int32_t* in_src, const int32_t* in_eid, float* in5, float* mean_v, int32_t* arg,
@@ -941,6 +957,13 @@ int gt_pna_aggregate_fwd_uv(const float* UV, const float* x, int64_t num_nodes, 
 int gt_pna_aggregate_bwd_uv(const float* UV, const float* in5, const float* mean_v, const int32_t* arg, const float* d_in5,
                             int64_t num_nodes, int64_t dim, int towers, const int32_t* in_ptr, const int32_t* out_ptr,
                             const int32_t* out_dst, const int32_t* out_eid, float* dUV, float* dxpart, gt_stream_t stream);
+/* the same pair with `slots` = K (4 or 6): operand and its gradient [N][T][(1+K) F] = [x_t | mean | max | min | std (| sum | var)] */
+int gt_pna_aggregate_fwd_uv_k(const float* UV, const float* x, int64_t num_nodes, int64_t dim, int towers, int slots,
+                              const int32_t* in_ptr, const int32_t* in_src, const int32_t* in_eid, float* operand, float* mean_v,
+                              int32_t* arg, gt_stream_t stream);
+int gt_pna_aggregate_bwd_uv_k(const float* UV, const float* operand, const float* mean_v, const int32_t* arg, const float* d_operand,
+                              int64_t num_nodes, int64_t dim, int towers, int slots, const int32_t* in_ptr, const int32_t* out_ptr,
+                              const int32_t* out_dst, const int32_t* out_eid, float* dUV, float* dxpart, gt_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------------
  * Whole-model driver: ONE C call per direction for the training step's forward and backward.
