@@ -70,6 +70,13 @@ SIGNATURES = {
     "gt_graph_pool_workspace_bytes": (_sz, [_i, _i64, _i64]),
     "gt_graph_pool_fwd": (_i, [_i, _i, _p, _p, _i64, _i64, _i64, _p, _p, _p, _sz, _p]),
     "gt_graph_pool_bwd": (_i, [_i, _i, _p, _p, _p, _p, _i64, _i64, _i64, _p, _p]),
+    "gt_head_group_workspace_bytes": (_sz, [_i64, _i64, _i64, _i64]),
+    "gt_head_group_fwd": (_i, [_i, _p, _i64, _p, _p, _p, _i64, _i64, _i64, _i64, _i64, _p]),
+    "gt_head_group_bwd": (_i, [_i, _p, _i64, _p, _p, _i64, _i, _p, _i64, _p, _p, _i64, _i64, _i64, _i64, _p, _sz, _p]),
+    "gt_head_mlp_workspace_bytes": (_sz, [_i64, _i64, _i64]),
+    "gt_head_mlp_fwd": (_i, [_i, _p, _i64, _p, _p, _p, _p, _p, _p, _p, _p, _p, _i64, _i64, _i64, _i64, _i64, _i64, _p]),
+    "gt_head_mlp_bwd": (_i, [_i, _p, _i64, _p, _p, _p, _p, _p, _p, _i64, _p, _i64, _p, _p, _p, _p, _p, _p, _i64, _i64, _i64, _i64, _i64,
+                             _p, _sz, _p]),
     "gt_seq_gather": (_i, [_i, _p, _p, _p, _p, _i64, _i64, _i64, _i, _i64, _p, _p, _p]),
     "gt_seq_scatter": (_i, [_i, _p, _p, _p, _p, _p, _i64, _i64, _i, _i64, _i64, _p, _p, _p]),
     "gt_batchnorm_workspace_bytes": (_sz, [_i64, _i64]),

@@ -90,6 +90,7 @@ struct Ctx {
   size_t o_h[MAXL + 1], o_x0, o_vn[MAXL], o_vn_saved[MAXL], o_conv_saved[MAXL], o_cat, o_hn, o_tok, o_xin, o_st0, o_xe[MAXL],
       o_enc_saved[MAXL], o_hgin, o_sto, o_eplan, o_esort_ws, o_ne_x, o_ne_w, o_hg, o_ws, o_ws2, o_wt[MAXL], o_g2t_wt;
   size_t o_scales, q_dimg;
+  size_t o_hid, o_hid2;   // gt_model::head_kind: the saved hidden activations (1: a1 [B][h1], a2 [B][h2]; 2: the stacked hidden rows [B][pos * D])
   size_t o_arg, o_pool_ws, pool_ws_bytes;   // read-out mode: the max's winning rows [B][D] int32, gt_graph_pool_fwd's workspace (o_hg: the pooled rows [B][D])
   size_t o_graph_ptr, o_node_graph, o_in_ptr, o_out_ptr, o_idx, o_dd, o_status, o_prep_ws, o_lay, o_lay_meta;
   size_t ws_bytes, ws2_bytes, eplan_bytes, esort_ws_bytes, prep_ws_bytes, arena_bytes;
@@ -108,7 +109,7 @@ struct Ctx {
   size_t q_d_hgin, q_dyp;
   size_t q_defer, defer_bytes, defer_small;   // defer_small: only partial buffers up to this size join the section (0 = all)   // the arena of the backward's deferred partial-sum reduces (gt_defer_begin)
   size_t q_d_hg, q_dtok[2], q_d_hn, q_d_cls, q_d_rep, q_dA, q_dB, q_dC, q_dJ, q_dvn[4], q_ne_dw, q_bnpart[MAXL], q_heads_ws,
-      q_ws[2], q_ws2, q_ws3;
+      q_ws[2], q_ws2, q_ws3, q_d_hid;
   size_t bws_bytes, heads_ws_bytes, seg_ws_bytes, barena_bytes;
   // what one backward stage leaves for the next (the stages may come as separate calls)
   char* bb;
@@ -126,10 +127,19 @@ int model_check(const char* fn, const gt_model* m) {
     gt_set_error("%s: layer / table counts out of range", fn);
     return GT_ERR_INVALID_ARG;
   }
-  if (ro && ((m->readout != GT_POOL_SUM && m->readout != GT_POOL_MEAN && m->readout != GT_POOL_MAX) || m->jk_cat || m->pe ||
-             (m->conv != GT_CONV_GCN && m->conv != GT_CONV_GIN))) {
-    gt_set_error("%s: the read-out mode takes a GT_POOL_* kind, GCN or GIN layers, JK = last and no positional encoding", fn);
+  // (the read-out mode takes every conv kind: the PNA stack under its own conditions, checked below)
+  if (ro && ((m->readout != GT_POOL_SUM && m->readout != GT_POOL_MEAN && m->readout != GT_POOL_MAX) || m->jk_cat || m->pe)) {
+    gt_set_error("%s: the read-out mode takes a GT_POOL_* kind, JK = last and no positional encoding", fn);
     return GT_ERR_INVALID_ARG;
+  }
+  if (m->head_kind) {   // the PNA baseline's heads (csrc/mlp_heads.hip): their shape limits are asked here, once
+    const bool mlp = m->head_kind == 1 && m->head_h1 >= 1 && m->head_h1 <= 64 && m->head_h2 >= 1 && m->head_h2 <= 64 && m->D <= 1024 &&
+                     m->hid2_w && m->hid2_b && m->off_hid2_w >= 0 && m->off_hid2_b >= 0;
+    const bool pos = m->head_kind == 2 && m->head_pos >= 1 && m->head_pos <= 16 && m->Nh % m->head_pos == 0 && m->D % 16 == 0 && m->D <= 512;
+    if (!ro || !(mlp || pos) || !m->hid_w || !m->hid_b || m->off_hid_w < 0 || m->off_hid_b < 0) {
+      gt_set_error("%s: head kind %d needs the read-out mode, its hidden layers and widths within the head kernels' limits", fn, m->head_kind);
+      return GT_ERR_INVALID_ARG;
+    }
   }
   if (!m->conv_layers || (m->n_enc && !m->enc) || (m->has_vn && m->L > 1 && !m->vn)) { gt_set_error("%s: null descriptor array", fn); return GT_ERR_INVALID_ARG; }
   if (m->D <= 0 || m->D % 4 || (!ro && (m->d <= 0 || m->d % 8))) { gt_set_error("%s: bad widths", fn); return GT_ERR_INVALID_ARG; }
@@ -455,6 +465,12 @@ void prepare_forward_arena(const gt_model* m, const gt_model_batch* b, Ctx* c) {
     c->o_arg = a.take(m->readout == GT_POOL_MAX ? (size_t)B * D * 4 : 0);
     c->pool_ws_bytes = gt_graph_pool_workspace_bytes(m->readout, N, D);
     c->o_pool_ws = a.take(c->pool_ws_bytes);
+    if (m->head_kind == 1) {
+      c->o_hid = a.take((size_t)B * m->head_h1 * 4);
+      c->o_hid2 = a.take((size_t)B * m->head_h2 * 4);
+    } else if (m->head_kind == 2) {
+      c->o_hid = a.take((size_t)B * m->head_pos * D * 4);
+    }
   }
   if (m->conv == GT_CONV_PNA) c->o_scales = a.take((size_t)N * c->pna[0].S * 4);
   size_t ws = 256, ws2 = 256;
@@ -508,7 +524,8 @@ void prepare_backward_arena(const gt_model* m, const gt_model_batch* b, Ctx* c) 
   for (int i = 0; i < nenc; ++i)
     enc_ws = std::max(enc_ws, i == nenc - 1 ? gt_encoder_layer_pooled_workspace_bytes(&c->enc[i]) : gt_encoder_layer_workspace_bytes(&c->enc[i]));
   const size_t ln_ws = ro ? 0 : std::max(gt_layernorm_bwd_workspace_bytes(rows, d), gt_layernorm_bwd_workspace_bytes(B, d));
-  const size_t lin_ws = std::max(gt_linear_bwd_workspace_bytes(c->compute, B, m->Nh, hk), ro ? (size_t)0 : gt_linear_bwd_workspace_bytes(c->compute, N, d, Kc));
+  size_t lin_ws = std::max(gt_linear_bwd_workspace_bytes(c->compute, B, m->Nh, hk), ro ? (size_t)0 : gt_linear_bwd_workspace_bytes(c->compute, N, d, Kc));
+  if (m->head_kind == 2) lin_ws = std::max(lin_ws, gt_linear_bwd_workspace_bytes(c->compute, B, m->head_pos * D, D));   // the stacked hidden layers
   const int64_t Kp = (int64_t)c4((size_t)m->ne_K);
   size_t emb_ws;
   if (m->embed_kind == 1) {
@@ -521,8 +538,11 @@ void prepare_backward_arena(const gt_model* m, const gt_model_batch* b, Ctx* c) 
   }
   c->bws_bytes = std::max(std::max(std::max(c->ws_bytes, enc_ws), std::max(ln_ws, lin_ws)), emb_ws);
   for (int l = 0; l + 1 < L; ++l) c->q_bnpart[l] = q.take(c->k.fuse_bn ? (size_t)c->k.bn_rows * 2 * D * 4 : 0);
-  c->heads_ws_bytes = gt_linear_bwd_workspace_bytes(c->compute, B, m->Nh, hk);
+  c->heads_ws_bytes = m->head_kind == 1   ? gt_head_mlp_workspace_bytes(B, m->head_h1, m->head_h2)
+                      : m->head_kind == 2 ? gt_head_group_workspace_bytes(B, m->head_pos, D, m->Nh / m->head_pos)
+                                          : gt_linear_bwd_workspace_bytes(c->compute, B, m->Nh, hk);
   c->q_heads_ws = q.take(c->heads_ws_bytes);
+  c->q_d_hid = q.take(m->head_kind == 2 ? (size_t)B * m->head_pos * D * 4 : 0);
   c->q_ws[0] = q.take(c->bws_bytes);
   c->q_ws[1] = q.take(c->bws_bytes);
   c->q_ws2 = q.take(c->ws2_bytes);
@@ -627,7 +647,8 @@ extern "C" int gt_model_grad_ranges(const gt_model* m, int64_t* lo3, int64_t* hi
   GT_TRY(model_check("gt_model_grad_ranges", m));
   GT_CHECK_ARG(lo3 && hi3, "null output");
   const int64_t gnn_lo = m->has_vn ? m->off_vn_emb : m->off_conv[0];
-  const int64_t tail = m->readout ? m->off_head_w : m->off_g2t_w;   // (read-out mode: no gnn2transformer, the heads follow message passing)
+  // (read-out mode: no gnn2transformer, the heads follow message passing; their hidden layers lead the head block)
+  const int64_t tail = m->readout ? (m->head_kind ? m->off_hid_w : m->off_head_w) : m->off_g2t_w;
   lo3[0] = tail;   hi3[0] = m->grad_total;
   lo3[1] = gnn_lo; hi3[1] = tail;
   lo3[2] = 0;            hi3[2] = gnn_lo;
@@ -654,6 +675,7 @@ extern "C" int gt_model_prepare(const gt_model* m, const gt_model_batch* b, void
   c->build_graph = b->graph_ptr == nullptr;
   if (m->readout) {   // no token layout (rows = num_work = 0, no staging-ring slot), no encoder weight images
     GT_CHECK_ARG(!b->gnn_frozen, "the read-out mode has no frozen message-passing stack (models/gnn.py has no freeze_gnn)");
+    GT_CHECK_ARG(m->head_kind != 2 || b->B <= 4096, "the per-position heads take at most 4096 graphs per batch");
     c->in.use_w3 = b->use_w3 ? 1 : 0;
     c->in.use_w1 = 0;
     c->exact = 1;
@@ -790,7 +812,16 @@ extern "C" int gt_model_forward(const gt_model* m, void* ctx_, void* arena, floa
     // ---- read-out + prediction heads   (models/gnn.py:107-115): the pooled rows [B][D], then one GEMM over the stacked head weights
     GT_TRY(gt_graph_pool_fwd(m->readout, GT_F32, c->h_last, g.graph_ptr, N, B, D, P(c->o_hg), m->readout == GT_POOL_MAX ? (int32_t*)P(c->o_arg) : nullptr,
                              P(c->o_pool_ws), c->pool_ws_bytes, st));
-    GT_TRY(gt_linear_fwd_ld(GT_F32, GT_F32, compute, P(c->o_hg), m->head_w, m->head_b, logits, B, m->Nh, D, m->ldy, 0, 0.f, 0, st));
+    if (m->head_kind == 1) {   // models/pna.py:53-60, :100: one launch, the two hidden activations saved for the backward
+      GT_TRY(gt_head_mlp_fwd(compute, (const float*)P(c->o_hg), D, m->hid_w, m->hid_b, m->hid2_w, m->hid2_b, m->head_w, m->head_b,
+                             (float*)P(c->o_hid), (float*)P(c->o_hid2), logits, m->ldy, B, D, m->head_h1, m->head_h2, m->Nh, st));
+    } else if (m->head_kind == 2) {   // models/pna.py:62-71, :101-104: the stacked hidden layers with the ReLU epilogue, then the grouped output layer
+      const int64_t Lp = m->head_pos;
+      GT_TRY(gt_linear_fwd(GT_F32, GT_F32, compute, P(c->o_hg), m->hid_w, m->hid_b, P(c->o_hid), B, Lp * D, D, 1, 0.f, 0, st));
+      GT_TRY(gt_head_group_fwd(compute, (const float*)P(c->o_hid), Lp * D, m->head_w, m->head_b, logits, m->ldy, B, Lp, D, m->Nh / Lp, st));
+    } else {
+      GT_TRY(gt_linear_fwd_ld(GT_F32, GT_F32, compute, P(c->o_hg), m->head_w, m->head_b, logits, B, m->Nh, D, m->ldy, 0, 0.f, 0, st));
+    }
     if (k.esort && m->st_dw) GT_TRY(gt_stream_wait_event(st, m->ev_sort[1]));   // the closing join of the side streams, as below
     else if (k.want_wt && m->st_dw) GT_TRY(gt_stream_wait_event(st, m->ev_wt[1]));
     return GT_OK;
@@ -913,10 +944,23 @@ int Bwd::encoder(const float* dlogits, bool frozen) const {
   const size_t ws_bytes = c->bws_bytes;
   if (m->readout) {   // heads (dW forked, dX) on the pooled rows [B][D], then the pooling's backward: d h_list[-1] for stage 2
     const int64_t D = m->D;
-    GT_TRY(gt_linear_bwd_dw_forked(GT_F32, GT_F32, compute, P(c->o_hg), m->head_w, dlogits, nullptr, G + m->off_head_w, G + m->off_head_b, B,
-                                   m->Nh, D, D, m->ldy, 0.f, Q(c->q_heads_ws), c->heads_ws_bytes, st));
-    GT_TRY(gt_linear_bwd_ld(GT_F32, GT_F32, compute, P(c->o_hg), m->head_w, dlogits, nullptr, nullptr, nullptr, Q(c->q_d_hg), nullptr, nullptr,
-                            B, m->Nh, D, m->ldy, 0.f, W(), ws_bytes, st));
+    if (m->head_kind == 1) {
+      GT_TRY(gt_head_mlp_bwd(compute, (const float*)P(c->o_hg), D, m->hid_w, m->hid2_w, m->head_w, (const float*)P(c->o_hid),
+                             (const float*)P(c->o_hid2), dlogits, m->ldy, (float*)Q(c->q_d_hg), D, G + m->off_hid_w, G + m->off_hid_b,
+                             G + m->off_hid2_w, G + m->off_hid2_b, G + m->off_head_w, G + m->off_head_b, B, D, m->head_h1, m->head_h2, m->Nh,
+                             Q(c->q_heads_ws), c->heads_ws_bytes, st));
+    } else if (m->head_kind == 2) {   // the output layers gate the hidden rows' gradient themselves (relu_mask): the hidden GEMM gets none
+      const int64_t Lp = m->head_pos;
+      GT_TRY(gt_head_group_bwd(compute, (const float*)P(c->o_hid), Lp * D, m->head_w, dlogits, m->ldy, 1, (float*)Q(c->q_d_hid), Lp * D,
+                               G + m->off_head_w, G + m->off_head_b, B, Lp, D, m->Nh / Lp, Q(c->q_heads_ws), c->heads_ws_bytes, st));
+      GT_TRY(gt_linear_bwd(GT_F32, GT_F32, compute, P(c->o_hg), m->hid_w, Q(c->q_d_hid), nullptr, nullptr, nullptr, Q(c->q_d_hg),
+                           G + m->off_hid_w, G + m->off_hid_b, B, Lp * D, D, 0.f, W(), ws_bytes, st));
+    } else {
+      GT_TRY(gt_linear_bwd_dw_forked(GT_F32, GT_F32, compute, P(c->o_hg), m->head_w, dlogits, nullptr, G + m->off_head_w, G + m->off_head_b, B,
+                                     m->Nh, D, D, m->ldy, 0.f, Q(c->q_heads_ws), c->heads_ws_bytes, st));
+      GT_TRY(gt_linear_bwd_ld(GT_F32, GT_F32, compute, P(c->o_hg), m->head_w, dlogits, nullptr, nullptr, nullptr, Q(c->q_d_hg), nullptr, nullptr,
+                              B, m->Nh, D, m->ldy, 0.f, W(), ws_bytes, st));
+    }
     GT_TRY(gt_graph_pool_bwd(m->readout, GT_F32, Q(c->q_d_hg), m->readout == GT_POOL_MAX ? (const int32_t*)P(c->o_arg) : nullptr, c->g.graph_ptr,
                              c->g.node_graph, N, B, D, Q(c->q_d_rep), st));
     c->dy = Q(c->q_d_rep);

@@ -20,6 +20,8 @@ Covered configuration (everything else keeps using the module path, see `eligibl
   The GNN baseline (models/gnn.py: `GNN`) runs the driver's read-out mode (gt_model::readout): the same message-passing stack (GCN /
   GIN, JK = last), then sum / mean / max pooling per graph and the heads -- no gnn2transformer, token layout, staging ring or encoder
   weight images; every parameter trainable.
+  The PNA baseline (models/pna.py: `PNANet`) runs the same mode over the PNA stack, with its own heads (gt_model::head_kind,
+  csrc/mlp_heads.hip): the narrow MLP (max_seq_len None) or the per-position two-layer heads (gnn_emb_dim a multiple of 16 up to 512).
 Reference call path: trainers/base_trainer.py:29-36 -> models/gnn_transformer.py:88-127 -> modules/gnn_module.py:181-224 ->
 modules/transformer_encoder.py:42-61.
 """
@@ -54,11 +56,20 @@ def _c4(n):
 
 
 def readout_kind(model):
-    """GT_POOL_* of a `models.gnn.GNN` (the driver's read-out mode: message passing -> per-graph pooling -> heads), 0 for the token-path
-    models"""
+    """GT_POOL_* of a `models.gnn.GNN` or a `models.pna.PNANet` (the driver's read-out mode: message passing -> per-graph pooling ->
+    heads), 0 for the token-path models"""
     from .models.gnn import GNN
+    from .models.pna import PNANet
     from .ops import POOL_KINDS
-    return POOL_KINDS[model.graph_pooling] if isinstance(model, GNN) else 0
+    return POOL_KINDS[model.graph_pooling] if isinstance(model, (GNN, PNANet)) else 0
+
+
+def head_kind(model):
+    """gt_model::head_kind: 0 the linear heads, 1 the narrow MLP of `PNANet` (max_seq_len None), 2 its per-position two-layer heads"""
+    from .models.pna import PNANet
+    if not isinstance(model, PNANet):
+        return 0
+    return 1 if model.max_seq_len is None else 2
 
 
 # ---- mirrors of the driver's structs (include/graphtrans_hip.h; sizes checked against gt_model_abi_sizes at first use) ----------
@@ -84,7 +95,10 @@ class ModelDesc(C.Structure):   # gt_model
                 ("ev_prep_begin", _vp), ("ev_graph", _vp), ("ev_w1", _vp), ("w3", ImageSet), ("w3_enc", ImageSet), ("w1", ImageSet),
                 ("pna_src", _vp), ("pna_img", _vp), ("pna_map", _vp), ("pna_inv", _vp), ("pna_n_img", _i64), ("pna_n_src", _i64),
                 ("off_pna_src", _i64), ("pna_img_off", (_i64 * 4) * MAXL), ("pna_kinds", _i32 * 8), ("pna_avg_log", _f32),
-                ("pna_avg_lin", _f32), ("readout", _i32), ("pad_readout_", _i32), ("pe", _vp), ("pe_rows", _i64)]
+                ("pna_avg_lin", _f32)] + [(k, _i32) for k in ("head_kind", "head_h1", "head_h2", "head_pos")] + \
+               [(k, _vp) for k in ("hid_w", "hid_b", "hid2_w", "hid2_b")] + \
+               [(k, _i64) for k in ("off_hid_w", "off_hid_b", "off_hid2_w", "off_hid2_b")] + \
+               [("readout", _i32), ("pad_readout_", _i32), ("pe", _vp), ("pe_rows", _i64)]
 
 
 class BatchDesc(C.Structure):   # gt_model_batch
@@ -270,7 +284,32 @@ class _Plan:
         self.enc_desc = (layers.EncoderLayerDesc * 1)()
         if not self.readout:
             self._init_encoder(model, enc, seg, block)
-        if model.max_seq_len is None:
+        # ---- the head block: hidden weights, hidden biases (PNANet only), output weights, output biases
+        self.head_kind = head_kind(model)
+        cm.head_kind = self.head_kind
+        cm.off_hid_w = cm.off_hid_b = cm.off_hid2_w = cm.off_hid2_b = -1
+        self.hid_flat = ()
+        if self.head_kind == 1:     # mlp = Linear(D, 35) -> ReLU -> Linear(35, 17) -> ReLU -> Linear(17, T)  (models/pna.py:53-60)
+            l1, l2, l3 = model.mlp[0], model.mlp[2], model.mlp[4]
+            cm.off_hid_w, cm.off_hid2_w, cm.off_hid_b, cm.off_hid2_b = seg(l1.weight), seg(l2.weight), seg(l1.bias), seg(l2.bias)
+            cm.head_h1, cm.head_h2 = l1.out_features, l2.out_features
+            cm.hid_w, cm.hid_b, cm.hid2_w, cm.hid2_b = (t.data_ptr() for t in (l1.weight, l1.bias, l2.weight, l2.bias))
+            self.heads = [l3]
+        elif self.head_kind == 2:   # per position Linear(D, D) -> ReLU -> Linear(D, T)  (models/pna.py:62-71): the hidden layers' storage
+            hid = [seq[0] for seq in model.graph_pred_linear_list]   # becomes the stacked [L*D][D] matrix, as the output layers' below
+            cm.head_pos = len(hid)
+            cm.off_hid_w = self.total
+            for h in hid:
+                self.params.append((h.weight, self.total))
+                self.total += h.weight.numel()
+            cm.off_hid_b = self.total
+            for h in hid:
+                self.params.append((h.bias, self.total))
+                self.total += h.bias.numel()
+            self.hid_flat = (_rehome([h.weight for h in hid])[0], _rehome([h.bias for h in hid])[0])
+            cm.hid_w, cm.hid_b = self.hid_flat[0].data_ptr(), self.hid_flat[1].data_ptr()
+            self.heads = [seq[2] for seq in model.graph_pred_linear_list]
+        elif model.max_seq_len is None:
             self.heads = [model.graph_pred_linear]
         else:
             self.heads = list(model.graph_pred_linear_list)
@@ -853,7 +892,7 @@ def _eligible_static(model):
     except Exception:
         return False
     if hasattr(gnn, "layers"):
-        return False if ro else _eligible_static_pna(model)
+        return _eligible_static_pna_readout(model) if ro else _eligible_static_pna(model)
     try:
         if ro:
             if gnn.JK != "last" or gnn.num_layer > MAXL:
@@ -951,33 +990,63 @@ def _encoder_ok(enc):
 def _eligible_static_pna(model):
     """PNATransformer (models/pna_transformer.py:16-118) on the fused path: PNANodeEmbedding with the residual connection, towers
     that divide the input, single-layer pre / post nets, packed token layout."""
-    from .modules.norm import BatchNorm1d
-    from .modules.pna.pna_module import PNAConv, _AGG_SLOT
     gnn, enc = model.gnn_node, model.transformer_encoder
     try:
         if not (model.pooling in ("cls", "last") and getattr(model, "layout", "auto") != "padded" and len(enc.transformer.layers) > 0):
             return False
-        convs = list(gnn.layers)
-        if not convs or len(convs) > MAXL or len(enc.transformer.layers) > MAXL or not gnn.residual:
+        if len(enc.transformer.layers) > MAXL or not _pna_convs_ok(gnn):
             return False
-        c0 = convs[0]
-        for c in convs:
-            if not (isinstance(c, PNAConv) and c.divide_input and c.in_channels == c.out_channels == c0.in_channels and c.towers == c0.towers
-                    and c.F_in == c.F_out and c.aggregators == c0.aggregators and c.scalers == c0.scalers and c.avg_deg == c0.avg_deg):
-                return False
-        if len(c0._blocks) > 8 or any(a not in _AGG_SLOT for a in c0.aggregators) or c0.in_channels > 1024:
-            return False
-        if any(b not in _Plan._SCALER_KIND for b in c0._blocks):
-            return False
-        for bn in gnn.batch_norms:
-            m = getattr(bn, "module", None)
-            if not (isinstance(m, BatchNorm1d) and m.affine and m.track_running_stats and m.momentum is not None):
-                return False
-        if model.gnn2transformer.in_features != c0.in_channels or c0.in_channels % 4 or c0.F_in % 4:
+        if model.gnn2transformer.in_features != gnn.layers[0].in_channels:
             return False
         return _eligible_static_rest(model)
     except Exception:
         return False
+
+
+def _eligible_static_pna_readout(model):
+    """PNANet (models/pna.py:20-104) on the fused path: the PNA conv checks of `_eligible_static_pna`, nothing about an encoder, and
+    the widths the head kernels take (csrc/mlp_heads.hip)."""
+    gnn = model.gnn_node
+    try:
+        if not _pna_convs_ok(gnn):
+            return False
+        D = gnn.layers[0].in_channels
+        if head_kind(model) == 1:
+            l1, l2, l3 = model.mlp[0], model.mlp[2], model.mlp[4]
+            if not (l1.in_features == D and max(l1.out_features, l2.out_features) <= 64 and all(m.bias is not None for m in (l1, l2, l3))):
+                return False
+        else:
+            heads = list(model.graph_pred_linear_list)
+            if not (1 <= len(heads) <= 16 and D % 16 == 0 and D <= 512):
+                return False
+            if any(seq[0].in_features != D or seq[0].out_features != D or seq[0].bias is None or seq[2].bias is None for seq in heads):
+                return False
+        return _eligible_static_rest(model)
+    except Exception:
+        return False
+
+
+def _pna_convs_ok(gnn):
+    """what the driver's PNA stack asks of a PNANodeEmbedding (called inside the callers' try)"""
+    from .modules.norm import BatchNorm1d
+    from .modules.pna.pna_module import PNAConv, _AGG_SLOT
+    convs = list(gnn.layers)
+    if not convs or len(convs) > MAXL or not gnn.residual:
+        return False
+    c0 = convs[0]
+    for c in convs:
+        if not (isinstance(c, PNAConv) and c.divide_input and c.in_channels == c.out_channels == c0.in_channels and c.towers == c0.towers
+                and c.F_in == c.F_out and c.aggregators == c0.aggregators and c.scalers == c0.scalers and c.avg_deg == c0.avg_deg):
+            return False
+    if len(c0._blocks) > 8 or any(a not in _AGG_SLOT for a in c0.aggregators) or c0.in_channels > 1024:
+        return False
+    if any(b not in _Plan._SCALER_KIND for b in c0._blocks):
+        return False
+    for bn in gnn.batch_norms:
+        m = getattr(bn, "module", None)
+        if not (isinstance(m, BatchNorm1d) and m.affine and m.track_running_stats and m.momentum is not None):
+            return False
+    return not (c0.in_channels % 4 or c0.F_in % 4)
 
 
 # ---------------------------------------------------------------------------------------------------

@@ -17,7 +17,7 @@ import torch
 import torch.nn as nn
 
 from ... import ops
-from ..gnn_module import batch_structure
+from ..gnn_module import _gnn_seed, batch_structure, layer_seed
 from ..norm import BatchNorm1d
 
 _AGG_SLOT = {"mean": 0, "max": 1, "min": 2, "std": 3, "sum": 4, "var": 5}
@@ -70,7 +70,7 @@ class PNAConv(nn.Module):
         # the post-Linear is evaluated per scaler block (see forward); the x_i columns and the bias are NOT scaled, so
         # they ride in a block of their own unless the first scaler is the identity
         self._blocks = list(self.scalers) if self.scalers and self.scalers[0] == "identity" else [None] + list(self.scalers)
-        deg = torch.as_tensor(deg).to(torch.float)
+        deg = torch.as_tensor(deg, device="cpu").to(torch.float)   # (host statistics: also under a `torch.device("meta")` construction)
         # avg_deg over the degree HISTOGRAM tensor, exactly as PyG 1.6.3 / modules/pna_layer.py:92-97 do
         self.avg_deg = {"lin": deg.mean().item(), "log": (deg + 1).log().mean().item(), "exp": deg.exp().mean().item()}
         self.pre_nns = nn.ModuleList()
@@ -269,11 +269,12 @@ class PNANodeEmbedding(nn.Module):
         gs = batch_structure(batched_data)
         encoded_node = self.node_encoder(x) if node_depth is None else self.node_encoder(x, node_depth.view(-1))
         x = encoded_node + perturb if perturb is not None else encoded_node
-        for conv, batch_norm in zip(self.layers, self.batch_norms):
+        base_seed = _gnn_seed(self)   # one draw per forward, layer l's mask from layer_seed(base, l): the fused step's seeds (csrc/model.hip)
+        for l, (conv, batch_norm) in enumerate(zip(self.layers, self.batch_norms)):
             h = batch_norm(conv(x, edge_index, graph=gs), relu=True)  # F.relu(batch_norm(conv(x)))  (:73)
             if self.residual:
                 x = h + x
             else:  # the reference leaves x unchanged without the residual (h is dropped, :73-76)
                 x = x
-            x = ops.dropout(x, self.drop_ratio, training=self.training)   # F.dropout (:78)
+            x = ops.dropout(x, self.drop_ratio, training=self.training, seed=layer_seed(base_seed, l))   # F.dropout (:78)
         return x

@@ -1060,3 +1060,109 @@ def tower_linear(x, weight, bias=None):
         raise ValueError("tower_linear: x (M, T, K), weight (T, Nout, K)")
     compute = GT_BF16 if x.dtype == torch.bfloat16 else f32_compute_code()
     return _TowerLinear.apply(x, weight, bias, compute)
+
+
+# ------------------------------------------------------------------------------------------------
+# the PNA baseline's prediction heads (models/pna.py:53-71; csrc/mlp_heads.hip)
+# ------------------------------------------------------------------------------------------------
+def _head_compute():
+    return GT_BF16 if _MATMUL_DTYPE == torch.bfloat16 else GT_F32   # ("high" maps to fp32 here)
+
+
+class _HeadMlp(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x, w1, b1, w2, b2, w3, b3):
+        x = _dev(x, "x")
+        M, D = x.shape
+        p = [_f32(t) for t in (w1, b1, w2, b2, w3, b3)]
+        H1, H2, T = p[0].shape[0], p[2].shape[0], p[4].shape[0]
+        a1 = torch.empty((M, H1), dtype=torch.float32, device=x.device)
+        a2 = torch.empty((M, H2), dtype=torch.float32, device=x.device)
+        y = torch.empty((M, T), dtype=torch.float32, device=x.device)
+        _lib.launch("gt_head_mlp_fwd", _head_compute(), _ptr(x), D, *[_ptr(t) for t in p], _ptr(a1), _ptr(a2), _ptr(y), T, M, D, H1, H2, T,
+                    _stream())
+        ctx.save_for_backward(x, p[0], p[2], p[4], a1, a2)
+        ctx.dtypes = [t.dtype for t in (w1, b1, w2, b2, w3, b3)]
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        x, w1, w2, w3, a1, a2 = ctx.saved_tensors
+        M, D = x.shape
+        H1, H2, T = w1.shape[0], w2.shape[0], w3.shape[0]
+        dy = _dev(dy.float(), "grad")
+        dev = x.device
+        dx = torch.empty_like(x) if ctx.needs_input_grad[0] else None
+        g = [torch.empty(s, dtype=torch.float32, device=dev) for s in ((H1, D), (H1,), (H2, H1), (H2,), (T, H2), (T,))]
+        wsb = _lib.lib().gt_head_mlp_workspace_bytes(M, H1, H2)
+        ws = torch.empty(max(wsb, 16), dtype=torch.uint8, device=dev)
+        _lib.launch("gt_head_mlp_bwd", _head_compute(), _ptr(x), D, _ptr(w1), _ptr(w2), _ptr(w3), _ptr(a1), _ptr(a2), _ptr(dy), T, _ptr(dx), D,
+                    *[_ptr(t) for t in g], M, D, H1, H2, T, _ptr(ws), wsb, _stream())
+        return (dx,) + tuple(t.to(dt) if need else None for t, dt, need in zip(g, ctx.dtypes, ctx.needs_input_grad[1:]))
+
+
+def head_mlp(x, lin1, lin2, lin3):
+    """lin3(relu(lin2(relu(lin1(x))))) for three nn.Linear of any hidden widths up to 64 (the reference's 35 and 17) and any output
+    width: one launch forward, a row pass and a fixed-order parameter reduce backward (gt_head_mlp_*), plain fp32."""
+    if x.dim() != 2 or not x.is_cuda or x.dtype != torch.float32 or x.shape[1] != lin1.weight.shape[1]:
+        raise RuntimeError("graphtrans_amd.ops.head_mlp: expected a 2-D fp32 GPU tensor of %d features, got %s %s on %s (no CPU / eager "
+                           "fallback)" % (lin1.weight.shape[1], tuple(x.shape), x.dtype, x.device))
+    if lin2.weight.shape[1] != lin1.weight.shape[0] or lin3.weight.shape[1] != lin2.weight.shape[0]:
+        raise ValueError("head_mlp: the three layers do not chain")
+    return _HeadMlp.apply(x, lin1.weight, lin1.bias, lin2.weight, lin2.bias, lin3.weight, lin3.bias)
+
+
+class _HeadGroup(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, h, w, b, G, relu_mask):
+        h = _dev(h, "h")
+        M = h.shape[0]
+        K = h.shape[1] // G
+        T = w.shape[0] // G
+        w32, b32 = _f32(w), _f32(b)
+        ldy = (G * T + 3) // 4 * 4
+        y = torch.empty((M, ldy), dtype=torch.float32, device=h.device)
+        compute = _head_compute()
+        _lib.launch("gt_head_group_fwd", compute, _ptr(h), G * K, _ptr(w32), _ptr(b32), _ptr(y), ldy, M, G, K, T, _stream())
+        ctx.save_for_backward(h, w32)
+        ctx.cfg = (compute, G, K, T, ldy, bool(relu_mask), w.dtype, b.dtype)
+        return y[:, :G * T]   # (M, G * T) view with row stride ldy
+
+    @staticmethod
+    def backward(ctx, dy):
+        h, w32 = ctx.saved_tensors
+        compute, G, K, T, ldy, relu_mask, wdt, bdt = ctx.cfg
+        M, N = h.shape[0], G * T
+        dy = dy.float()
+        if not (dy.is_cuda and dy.stride(1) == 1 and dy.stride(0) >= N and dy.stride(0) % 4 == 0):   # else: rows of the loss's own pitch
+            full = torch.empty((M, ldy), dtype=torch.float32, device=h.device)
+            full[:, :N].copy_(dy)
+            dy = full[:, :N]
+        need_h, need_w = ctx.needs_input_grad[0], ctx.needs_input_grad[1] or ctx.needs_input_grad[2]
+        dev = h.device
+        dh = torch.empty_like(h) if need_h else None
+        dw = torch.empty((N, K), dtype=torch.float32, device=dev) if need_w else None
+        db = torch.empty(N, dtype=torch.float32, device=dev) if need_w else None
+        wsb = _lib.lib().gt_head_group_workspace_bytes(M, G, K, T) if need_h else 0
+        ws = torch.empty(max(wsb, 16), dtype=torch.uint8, device=dev)
+        _lib.launch("gt_head_group_bwd", compute, _ptr(h), G * K, _ptr(w32), _ptr(dy), dy.stride(0), int(relu_mask), _ptr(dh), G * K, _ptr(dw),
+                    _ptr(db), M, G, K, T, _ptr(ws), wsb, _stream())
+        return dh, (dw.to(wdt) if ctx.needs_input_grad[1] else None), (db.to(bdt) if ctx.needs_input_grad[2] else None), None, None
+
+
+def head_group(h, out_layers, relu_mask=False):
+    """The per-position output layers Linear(K, T) of models/pna.py:63-71 on the stacked hidden activations h (M, G * K) (head g reads
+    the columns [g*K, (g+1)*K)): G different products into ONE logits buffer (gt_head_group_*), returned as base_model.StackedHeads
+    -- head g at column g*T of rows padded to a multiple of 4, what losses.code2_loss expects.  K % 16 == 0, K <= 512; any T.
+    relu_mask: h is the output of a ReLU whose gradient gate this backward applies (leave it False behind ops.linear(act="relu"),
+    which gates its own)."""
+    from .models.base_model import StackedHeads
+    G = len(out_layers)
+    K, T = out_layers[0].weight.shape[1], out_layers[0].weight.shape[0]
+    if h.dim() != 2 or not h.is_cuda or h.dtype != torch.float32 or h.shape[1] != G * K:
+        raise RuntimeError("graphtrans_amd.ops.head_group: expected a 2-D fp32 GPU tensor of %d x %d features, got %s %s on %s (no CPU / "
+                           "eager fallback)" % (G, K, tuple(h.shape), h.dtype, h.device))
+    w = torch.cat([m.weight for m in out_layers], dim=0)
+    b = torch.cat([m.bias for m in out_layers], dim=0)
+    y = _HeadGroup.apply(h, w, b, G, relu_mask)
+    return StackedHeads(y.view(h.shape[0], G, T))

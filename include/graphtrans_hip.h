@@ -316,6 +316,41 @@ int gt_graph_pool_fwd(int kind, int dtype, const void* x, const int32_t* graph_p
 int gt_graph_pool_bwd(int kind, int dtype, const void* d_out, const int32_t* arg, const int32_t* graph_ptr,
                       const int32_t* node_graph, int64_t num_nodes, int64_t num_graphs, int64_t dim, void* dx, gt_stream_t stream);
 
+/* The prediction heads of the PNA baseline (models/pna.py:53-71; csrc/mlp_heads.hip).  fp32 storage, no atomics, every sum in a fixed
+ * order: two runs give the same bits.
+ *
+ * Position-grouped output layer -- G different (M, K) x (K, T) products into ONE logits buffer, head g at column g*T:
+ *   fwd  Y[b][g*T + n] = sum_k H[b][g*K + k] W[g*T + n][k] + bias[g*T + n]
+ *   bwd  dH[b][g*K + k] = (relu_mask && H[b][g*K + k] <= 0 ? 0 : 1) * sum_n dY[b][g*T + n] W[g*T + n][k]
+ *        dW[g*T + n][k] = sum_b dY[b][g*T + n] H[b][g*K + k]          dbias[c] = sum_b dY[b][c]   (fp32 sums of dY as stored)
+ *   H [M][ldh] (ldh >= G*K, % 4), W [G*T][K] contiguous, Y / dY [M][ldy] (ldy >= G*T, % 4; the columns [G*T, ldy) are never read or
+ *   written), dH [M][lddh]; H, W, dH and the workspace 16-byte aligned.  K % 16 == 0, 16 <= K <= 512 (else GT_ERR_UNSUPPORTED); any
+ *   T >= 1 (a head's first column is only 4-byte aligned: tiles never straddle two heads, Y / bias / dY are addressed element by
+ *   element); M <= 4096; G <= 16.  compute: GT_F32 = exact fp32 chains, GT_BF16 = each operand rounded once to bf16 with fp32
+ *   accumulation, GT_COMPUTE_F32_HIGH = GT_F32.  relu_mask: H is a ReLU's output whose gradient gate is applied here, once.  dH sums
+ *   over step ranges of T with fp32 partials in `workspace` (needed only with dh) and one fixed-order reduce.  dh, dw, dbias may be
+ *   NULL (dbias needs dw); dw / dbias are written, not accumulated into.
+ *
+ * Narrow MLP head -- y = W3 relu(W2 relu(W1 x + b1) + b2) + b3, plain fp32 FMA in every compute mode:
+ *   x [M][ldx] (D % 4 == 0, D <= 1024, ldx % 4 == 0; x and W1 16-byte aligned), W1 [H1][D], W2 [H2][H1], W3 [T][H2], 1 <= H1, H2 <= 64
+ *   (else GT_ERR_UNSUPPORTED), any T >= 1, y [M][ldy].  The forward is ONE launch and saves a1 [M][H1], a2 [M][H2] (after the ReLU).
+ *   The backward is one launch over row blocks (the gated deltas into `workspace`, dx [M][lddx] or NULL) and one fixed-order reduce
+ *   over the rows that writes the six parameter gradients (all required). */
+size_t gt_head_group_workspace_bytes(int64_t M, int64_t G, int64_t K, int64_t T);
+int gt_head_group_fwd(int compute, const float* h, int64_t ldh, const float* w, const float* bias, float* y, int64_t ldy, int64_t M,
+                      int64_t G, int64_t K, int64_t T, gt_stream_t stream);
+int gt_head_group_bwd(int compute, const float* h, int64_t ldh, const float* w, const float* dy, int64_t lddy, int relu_mask, float* dh,
+                      int64_t lddh, float* dw, float* dbias, int64_t M, int64_t G, int64_t K, int64_t T, void* workspace,
+                      size_t workspace_bytes, gt_stream_t stream);
+size_t gt_head_mlp_workspace_bytes(int64_t M, int64_t H1, int64_t H2);
+int gt_head_mlp_fwd(int compute, const float* x, int64_t ldx, const float* w1, const float* b1, const float* w2, const float* b2,
+                    const float* w3, const float* b3, float* a1, float* a2, float* y, int64_t ldy, int64_t M, int64_t D, int64_t H1,
+                    int64_t H2, int64_t T, gt_stream_t stream);
+int gt_head_mlp_bwd(int compute, const float* x, int64_t ldx, const float* w1, const float* w2, const float* w3, const float* a1,
+                    const float* a2, const float* dy, int64_t lddy, float* dx, int64_t lddx, float* dw1, float* db1, float* dw2,
+                    float* db2, float* dw3, float* db3, int64_t M, int64_t D, int64_t H1, int64_t H2, int64_t T, void* workspace,
+                    size_t workspace_bytes, gt_stream_t stream);
+
 /* ---------------------------------------------------------------------------------------------
  * Sequence layout: flat node rows <-> transformer token rows.
  * Replaces pad_batch / unpad_batch (modules/utils.py:5-53) and the CLS concat
@@ -1040,9 +1075,23 @@ typedef struct gt_model {
   int64_t pna_img_off[GT_MODEL_MAX_LAYERS][4];
   int32_t pna_kinds[8];          /* degree scalers of the S output blocks (gt_pna_scales) */
   float pna_avg_log, pna_avg_lin;
+  /* The heads of the read-out mode (a zeroed struct gives 0; anything but 0 needs readout != 0).
+   *   0  the linear heads: head_w [Nh][D], head_b [Nh], one GEMM (the GNN baseline).
+   *   1  the narrow MLP of models/pna.py:53-60 (gt_head_mlp_*): hid_w [head_h1][D], hid_b, hid2_w [head_h2][head_h1], hid2_b, then
+   *      head_w [Nh][head_h2], head_b [Nh]; 1 <= head_h1, head_h2 <= 64, D <= 1024.
+   *   2  head_pos per-position heads Linear(D, D) -> ReLU -> Linear(D, Nh / head_pos) (models/pna.py:62-71): hid_w [head_pos * D][D] and
+   *      hid_b [head_pos * D] are the stacked hidden layers (one gt_linear_fwd with the ReLU epilogue), head_w [Nh][D] / head_b [Nh] the
+   *      stacked output layers (gt_head_group_*: head i at column i * Nh / head_pos of the logits); D % 16 == 0, D <= 512,
+   *      head_pos <= 16, at most 4096 graphs per batch.
+   * off_hid_*: offsets (floats) into the flat gradient buffer, -1 = absent.  The head block is laid out hidden weights, hidden biases,
+   * output weights, output biases: off_hid_w is its first float, and where range 0 of gt_model_grad_ranges starts. */
+  int32_t head_kind, head_h1, head_h2, head_pos;
+  const float *hid_w, *hid_b, *hid2_w, *hid2_b;
+  int64_t off_hid_w, off_hid_b, off_hid2_w, off_hid2_b;
   /* 0: the token path (a caller that zeroes the struct gets it).  GT_POOL_SUM | GT_POOL_MEAN | GT_POOL_MAX: the GNN baseline
    * (models/gnn.py:98-115) -- message passing, then gt_graph_pool_fwd over h_list[-1] and the heads on the pooled rows [B][D] (head_w is
-   * [Nh][D]).  Requires n_enc == 0, jk_cat == 0, conv GCN or GIN, no pe, gt_model_batch::gnn_frozen == 0; g2t / cls / norm / enc fields
+   * [Nh][D]; the PNA baseline, models/pna.py:94-104, with head_kind 1 or 2).  Requires n_enc == 0, jk_cat == 0, no pe, any conv kind
+   * (GT_CONV_PNA under its own conditions above), gt_model_batch::gnn_frozen == 0; g2t / cls / norm / enc fields
    * and w3_enc / w1 are not read, no token layout is built (gt_model_sizes: rows = num_work = 0) and no staging-ring slot is taken.
    * (In front of {pe, pe_rows}, which stay the struct's tail.) */
   int32_t readout, pad_readout_;
@@ -1115,7 +1164,8 @@ int gt_model_forward(const gt_model* model, void* ctx, void* arena, float* logit
 int gt_model_backward(const gt_model* model, void* ctx, const float* dlogits, float* grads, void* barena, int stages,
                       gt_stream_t stream);
 /* first / one-past-last float of the gradient range each stage completes: {g2t..total, gnn_lo..g2t, 0..gnn_lo}; with
- * gt_model::readout (no gnn2transformer) the heads' offset stands where g2t does: {heads..total, gnn_lo..heads, 0..gnn_lo} */
+ * gt_model::readout (no gnn2transformer) the heads' offset stands where g2t does: {heads..total, gnn_lo..heads, 0..gnn_lo}, heads =
+ * off_head_w, or off_hid_w (the hidden layers lead the head block) with gt_model::head_kind != 0 */
 int gt_model_grad_ranges(const gt_model* model, int64_t* lo3, int64_t* hi3);
 /* out4 = sizeof {gt_model, gt_model_batch, gt_image_set, gt_stage_ring}: a binding checks its mirror of the layouts */
 int gt_model_abi_sizes(int64_t* out4);
