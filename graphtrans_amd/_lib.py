@@ -40,6 +40,8 @@ SIGNATURES = {
     "gt_attr_rank": (_i, [_p, _i64, _p, _p]),
     "gt_collate_workspace_bytes": (_sz, [_i64]),
     "gt_collate": (_i, [_p, _p, _i64, _i64, _i64, _p, _p, _sz, _p]),
+    "gt_store_in_degree": (_i, [_p, _p, _p]),
+    "gt_degree_histogram": (_i, [_p, _p, _p, _i64, _i64, _p, _p]),
     "gt_graph_prep_workspace_bytes": (_sz, [_i64, _i64, _i64]),
     "gt_graph_prep": (_i, [_p, _p, _i64, _i64, _i64, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _sz, _p]),
     "gt_aggregate_fwd": (_i, [_i, _i, _i, _p, _i64, _i64, _i64, _p, _p, _p, _p, _p, _p, _p, _i64, _p, _p,

@@ -15,7 +15,7 @@ void gt_set_error(const char* fmt, ...) {
   va_end(ap);
 }
 
-extern "C" int gt_version(void) { return 100; /* 0.1.0 */ }
+extern "C" int gt_version(void) { return 101; /* 0.1.1: gt_graph_store / gt_collate_out grew (float features) */ }
 extern "C" const char* gt_last_error(void) { return g_err; }
 
 // ---- opt-in launch profiler ----------------------------------------------------------------------

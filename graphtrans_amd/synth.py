@@ -135,35 +135,63 @@ def molpcba_like(B=256, seed=0, num_tasks=128):
                    sizes, dict(y=torch.from_numpy(y)))
 
 
-def nci1_like(B=32, seed=0, num_features=37):
+def _nci1_graphs(B, seed, num_features):
     rng = np.random.default_rng(seed)
     sizes = np.clip(np.round(rng.normal(30, 13, B)), 3, 111).astype(np.int64)
-    xs, eis = [], []
+    graphs = []
     for n in sizes:
         n = int(n)
         x = np.zeros((n, num_features), np.float32)
         x[np.arange(n), rng.integers(0, num_features, n)] = 1.0
-        xs.append(x); eis.append(_random_undirected(rng, n, int(round(1.08 * n))))
+        graphs.append(dict(x=x, edge_index=_random_undirected(rng, n, int(round(1.08 * n)))))
     y = rng.integers(0, 2, B).astype(np.int64)
-    return _finish(xs, eis, None, sizes, dict(y=torch.from_numpy(y)))
+    for g, v in zip(graphs, y):
+        g["y"] = v.reshape(1)
+    return sizes, graphs
 
 
-def er_stress(B=256, seed=0, n=512, avg_deg=8.0, feat_dim=256, num_classes=2):
-    """BASELINE.json configs[4]: G(n, p=avg_deg/(n-1)), both directions stored; x (N,feat) f32
-    through a Linear node encoder; Code2-style 2-column {0,1} edge_attr."""
+def nci1_raw(B=32, seed=0, num_features=37):
+    """Raw graphs for data.GraphStore (TU datasets carry no per-sample transform, dataset/tud.py): float32 one-hot x, no edge
+    features; collating graphs 0..B-1 reproduces nci1_like(B, seed) exactly."""
+    return _nci1_graphs(B, seed, num_features)[1]
+
+
+def nci1_like(B=32, seed=0, num_features=37):
+    sizes, graphs = _nci1_graphs(B, seed, num_features)
+    y = np.concatenate([g["y"] for g in graphs], 0)
+    return _finish([g["x"] for g in graphs], [g["edge_index"] for g in graphs], None, sizes, dict(y=torch.from_numpy(y)))
+
+
+def _er_graphs(B, seed, n, avg_deg, feat_dim, num_classes):
     rng = np.random.default_rng(seed)
     p = avg_deg / (n - 1)
-    xs, eis, eas = [], [], []
+    graphs = []
     iu = np.triu_indices(n, 1)
     for _ in range(B):
         sel = rng.random(iu[0].size) < p
         e = np.stack([iu[0][sel], iu[1][sel]]).astype(np.int64)
         ei = np.concatenate([e, e[::-1]], axis=1)
-        eis.append(ei)
-        eas.append(rng.integers(0, 2, (ei.shape[1], 2)).astype(np.float32))
-        xs.append(rng.standard_normal((n, feat_dim), dtype=np.float32))
+        ea = rng.integers(0, 2, (ei.shape[1], 2)).astype(np.float32)
+        graphs.append(dict(x=rng.standard_normal((n, feat_dim), dtype=np.float32), edge_index=ei, edge_attr=ea))
     y = rng.integers(0, num_classes, B).astype(np.int64)
-    return _finish(xs, eis, eas, np.full(B, n, np.int64), dict(y=torch.from_numpy(y)))
+    for g, v in zip(graphs, y):
+        g["y"] = v.reshape(1)
+    return graphs
+
+
+def er_raw(B=256, seed=0, n=512, avg_deg=8.0, feat_dim=256, num_classes=2):
+    """Raw graphs for data.GraphStore: float32 x (n, feat_dim) and float32 edge_attr (E, 2), stored as they are (no
+    augmentation); collating graphs 0..B-1 reproduces er_stress(B, seed, ...) exactly."""
+    return _er_graphs(B, seed, n, avg_deg, feat_dim, num_classes)
+
+
+def er_stress(B=256, seed=0, n=512, avg_deg=8.0, feat_dim=256, num_classes=2):
+    """BASELINE.json configs[4]: G(n, p=avg_deg/(n-1)), both directions stored; x (N,feat) f32
+    through a Linear node encoder; Code2-style 2-column {0,1} edge_attr."""
+    graphs = _er_graphs(B, seed, n, avg_deg, feat_dim, num_classes)
+    y = np.concatenate([g["y"] for g in graphs], 0) if graphs else np.zeros(0, np.int64)
+    return _finish([g["x"] for g in graphs], [g["edge_index"] for g in graphs], [g["edge_attr"] for g in graphs],
+                   np.full(B, n, np.int64), dict(y=torch.from_numpy(y)))
 
 
 def tiny_mixed(seed=0, sizes=(7, 1, 12, 5), feat="code2", num_nodetypes=11, num_nodeattributes=13,

@@ -94,19 +94,38 @@ int gt_profile_get(int64_t index, char* name_out, int64_t name_cap, float* ms, i
  * Replaces: the per-sample `augment_edge` transform (dataset/utils.py:89-141, installed at
  * dataset/code.py:97-101) and PyG `Batch.from_data_list` behind the DataLoader (main.py:149-152).
  *
- * Store = per-graph slices of concatenated int64 arrays: node_ptr/edge_ptr [G+1]; x [Ns][x_cols];
- * node_depth [Ns] (optional); edge_src/edge_dst [Es] with node ids LOCAL to their graph; edge_attr
- * [Es][ea_cols] (optional); y [G][y_row_bytes] raw label rows (optional).  attr_rank [Ns+1] (optional) is
+ * Store = per-graph slices of concatenated arrays: node_ptr/edge_ptr [G+1] int64; node features [Ns][x_cols], EITHER int64 `x`
+ * OR float32 `x_f32` (TU datasets, dataset/tud.py: one-hot rows through an nn.Linear node encoder) -- exactly one of the two is
+ * set; node_depth [Ns] (optional); edge_src/edge_dst [Es] with node ids LOCAL to their graph; edge features [Es][ea_cols]
+ * (optional), int64 `edge_attr` OR float32 `edge_attr_f32`, at most one of the two; y [G][y_row_bytes] raw label rows
+ * (optional).  x_cols / ea_cols describe whichever array is set.  attr_rank [Ns+1] (optional) is
  * the exclusive prefix sum of (node_is_attributed == 1) over all store nodes, built once by
  * gt_attr_rank; when present the batch is AUGMENTED: per graph the output edges are
  * [ast, ast^-1, next-token, next-token^-1] and edge_attr_f32 [E][2] = (is next-token, is inverse),
- * exactly the reference's edge order and values; stored edge_attr is then ignored.
+ * exactly the reference's edge order and values; a stored int64 edge_attr is then ignored and a stored edge_attr_f32 is an error.
  *
- * gt_collate: graph_ids [B] (device) -> x [N][x_cols], node_depth [N], batch [N], ptr [B+1] (optional),
- * edge_index [2][E] (global ids), edge_attr_f32 or edge_attr_i64 [E][ea_cols], y [B][y_row_bytes].
+ * gt_collate: graph_ids [B] (device) -> x or x_f32 [N][x_cols] (the store's type), node_depth [N], batch [N], ptr [B+1]
+ * (optional), edge_index [2][E] (global ids), edge_attr_f32 or edge_attr_i64 [E][ea_cols], y [B][y_row_bytes].
+ * edge_attr_f32 is written by an augmenting store ([E][2]) and is the destination of a plain store's float edge_attr.
  * N and E are the totals over the selected graphs (the caller owns the allocations and knows the
  * per-graph sizes: E_i = e_i, or 2 e_i + 2 max(a_i - 1, 0) when augmenting); graphs that would not
- * fit the stated N / E are skipped rather than written out of bounds.  Integer-exact.
+ * fit the stated N / E are skipped rather than written out of bounds.  Integer-exact; float rows are copied bit for bit
+ * (one flat run per graph, 16-byte vectors where source and destination are 16-byte aligned, which holds for every graph when
+ * the column count is a multiple of 4 and the arrays themselves are aligned).
+ * GT_ERR_INVALID_ARG: both or neither of x / x_f32 in the store; both edge_attr and edge_attr_f32; edge_attr_f32 stored beside
+ * attr_rank; an output whose type is not the store's (out->x for x_f32 and the reverse, either edge_attr output for a store
+ * that holds the other type or none).
+ *
+ * PNA in-degree histogram (dataset/code.py:119-132 with bins 800, dataset/mol.py:70-81 with bins 10: a Python loop of
+ * `degree(edge_index[1], num_nodes)` + `bincount` over every training graph, on Code2 over the augmented edges):
+ *   gt_store_in_degree: deg [Ns] int32 = in-degree of every store node over the edges gt_collate emits for its graph (stored
+ *     edges; for an augmenting store also their inverses and the next-token chain in both directions).  One-off per store;
+ *     deg need not be cleared.
+ *   gt_degree_histogram: hist [bins + 1] int64, hist[d] = number of nodes with deg == d among the graphs graph_ids [num_graphs]
+ *     (device; a graph listed twice counts twice; NULL = graphs 0 .. num_graphs - 1), hist[bins] = nodes with deg >= bins (the
+ *     caller's overflow check).  hist is cleared by the call.  1 <= bins <= 8191 (the per-block counters live in LDS);
+ *     GT_ERR_UNSUPPORTED above.
+ * Both are integer atomics only: exact and independent of the order of execution.
  */
 typedef struct gt_graph_store {
   const int64_t* node_ptr;
@@ -122,17 +141,20 @@ typedef struct gt_graph_store {
   int64_t num_graphs;
   int32_t x_cols;
   int32_t ea_cols;
+  const float* x_f32;         /* float32 node features: set INSTEAD of x */
+  const float* edge_attr_f32; /* float32 edge features: set INSTEAD of edge_attr, plain stores only */
 } gt_graph_store;
 
 typedef struct gt_collate_out {
-  int64_t* x;
+  int64_t* x;            /* stores with int64 x */
   int64_t* node_depth;   /* optional */
   int64_t* batch;
   int64_t* ptr;          /* optional */
   int64_t* edge_index;
-  float* edge_attr_f32;  /* augmenting stores */
+  float* edge_attr_f32;  /* augmenting stores; plain stores with a float edge_attr */
   int64_t* edge_attr_i64; /* optional, plain stores */
   void* y;               /* optional */
+  float* x_f32;          /* stores with float32 x */
 } gt_collate_out;
 
 int gt_attr_rank(const int64_t* node_is_attributed, int64_t num_nodes, int64_t* rank, gt_stream_t stream);
@@ -140,6 +162,9 @@ size_t gt_collate_workspace_bytes(int64_t num_graphs);
 int gt_collate(const gt_graph_store* store, const int64_t* graph_ids, int64_t num_graphs, int64_t num_nodes,
                int64_t num_edges, const gt_collate_out* out, void* workspace, size_t workspace_bytes,
                gt_stream_t stream);
+int gt_store_in_degree(const gt_graph_store* store, int32_t* deg, gt_stream_t stream);
+int gt_degree_histogram(const gt_graph_store* store, const int32_t* deg, const int64_t* graph_ids, int64_t num_graphs,
+                        int64_t bins, int64_t* hist, gt_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------------
  * Graph structure, built once per collated batch.
