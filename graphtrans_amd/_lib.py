@@ -169,6 +169,11 @@ SIGNATURES = {
     "gt_xent_bwd": (_i, [_p, _p, _p, _p, _i64, _p, _i64, _i64, _i64, _i64, _p, _p]),
     "gt_bce_masked_fwd": (_i, [_p, _p, _i64, _i64, _i64, _i64, _p, _p, _p, _p, _p]),
     "gt_bce_masked_bwd": (_i, [_p, _p, _p, _p, _i64, _i64, _i64, _i64, _p, _p]),
+    "gt_eval_argmax": (_i, [_p, _i64, _i64, _i64, _i64, _i64, _p, _p]),
+    "gt_eval_seq_f1": (_i, [_p, _i64, _i64, _i64, _p, _p, _i64, _i64, _p, _p, _i64, _i64, _p]),
+    "gt_eval_rows_mean_f64": (_i, [_p, _i64, _p, _p]),
+    "gt_eval_count_correct": (_i, [_p, _p, _i64, _p, _p]),
+    "gt_eval_ap_sorted": (_i, [_p, _p, _i64, _i64, _i64, _p, _p, _p]),
     "gt_linear_bwd_workspace_bytes": (_sz, [_i, _i64, _i64, _i64]),
     "gt_linear_bwd": (_i, [_i, _i, _i, _p, _p, _p, _p, _p, _p, _p, _p, _p, _i64, _i64, _i64, _f, _p, _sz, _p]),
     # composite layers (descriptor structs are passed by pointer; see graphtrans_amd/layers.py)

@@ -192,6 +192,7 @@ class GraphStore:
         if y is not None:
             setattr(b, self.label_key, y)
         b._num_graphs, b._sizes = B, sizes
+        b._graph_ids = d_ids   # evaluate.Code2F1 looks the reference word sets up by these
         return b
 
     def batches(self, batch_size, ids=None, shuffle=False, drop_last=False, seed=None):

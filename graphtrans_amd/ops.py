@@ -1015,6 +1015,79 @@ def masked_bce(pred, y, den=None):
 
 
 # ------------------------------------------------------------------------------------------------
+# evaluation metrics (csrc/metrics.hip; graphtrans_amd/evaluate.py owns the buffers): every wrapper only enqueues
+# ------------------------------------------------------------------------------------------------
+def _eval_dev(t, dtype, name):
+    if not (isinstance(t, torch.Tensor) and t.is_cuda):
+        raise RuntimeError(f"{name} must be a GPU tensor: graphtrans_amd has no CPU fallback")
+    if t.dtype != dtype or not t.is_contiguous():
+        raise TypeError(f"{name}: contiguous {dtype} expected, got {t.dtype} with strides {tuple(t.stride())}")
+    return t
+
+
+def eval_argmax(logits, B, H, C, ld, head_stride, pred):
+    """pred[b][h] = torch.argmax(logits[b, h*head_stride : h*head_stride + C]) for fp32 logits whose row b starts ld floats
+    after row b - 1 (`logits`: any fp32 GPU tensor whose first element is logits[0][0]); pred: int32, B * H elements."""
+    if not logits.is_cuda or logits.dtype != torch.float32:
+        raise TypeError("eval_argmax: fp32 GPU logits expected (graphtrans_amd has no CPU fallback)")
+    _eval_dev(pred, torch.int32, "pred")
+    if pred.numel() < B * H:
+        raise ValueError("eval_argmax: pred holds fewer than B * H elements")
+    _lib.launch("gt_eval_argmax", _ptr(logits), B, H, C, ld, head_stride, _ptr(pred), _stream())
+    return pred
+
+
+def eval_seq_f1(pred, B, H, C, ref_ids, n_ref, rows, row_off, graph_ids=None):
+    """rows[row_off + b] = (precision, recall, F1) of graph b's decoded prediction against reference set graph_ids[b] (None: b)."""
+    _eval_dev(pred, torch.int32, "pred")
+    _eval_dev(ref_ids, torch.int32, "ref_ids")
+    _eval_dev(n_ref, torch.int32, "n_ref")
+    _eval_dev(rows, torch.float64, "rows")
+    if graph_ids is not None:
+        _eval_dev(graph_ids, torch.int64, "graph_ids")
+        if graph_ids.numel() < B:
+            raise ValueError("eval_seq_f1: fewer graph ids than graphs")
+    if pred.numel() < B * H or ref_ids.dim() != 2 or n_ref.numel() != ref_ids.shape[0] or rows.dim() != 2 or rows.shape[1] != 3:
+        raise ValueError("eval_seq_f1: pred [B][H], ref_ids [G][R], n_ref [G], rows [n][3] expected")
+    _lib.launch("gt_eval_seq_f1", _ptr(pred), B, H, C, _ptr(ref_ids), _ptr(n_ref), ref_ids.shape[1], ref_ids.shape[0],
+                _ptr(graph_ids), _ptr(rows), row_off, rows.shape[0], _stream())
+
+
+def eval_rows_mean(rows, n, out):
+    """out[0..3) = column means of rows[0..n), float64, in an order that depends on n alone"""
+    _eval_dev(rows, torch.float64, "rows")
+    _eval_dev(out, torch.float64, "out")
+    if rows.dim() != 2 or rows.shape[1] != 3 or not 0 < n <= rows.shape[0] or out.numel() < 3:
+        raise ValueError("eval_rows_mean: rows [>= n][3] with n >= 1 and out [3] expected")
+    _lib.launch("gt_eval_rows_mean_f64", _ptr(rows), n, _ptr(out), _stream())
+    return out
+
+
+def eval_count_correct(pred, y, B, count):
+    """count[0] += number of b < B with pred[b] == y[b] (pred int32, y int64, count int64 on the device)"""
+    _eval_dev(pred, torch.int32, "pred")
+    _eval_dev(y, torch.int64, "y")
+    _eval_dev(count, torch.int64, "count")
+    if pred.numel() < B or y.numel() < B or count.numel() < 1:
+        raise ValueError("eval_count_correct: pred and y hold fewer than B elements")
+    _lib.launch("gt_eval_count_correct", _ptr(pred), _ptr(y), B, _ptr(count), _stream())
+
+
+def eval_ap_sorted(scores, labels, n, ap, valid):
+    """ap[t], valid[t] of every task t: scores [T][ld >= n] fp32 sorted descending along dim 1, labels in the same order"""
+    if scores.dim() != 2 or scores.shape != labels.shape or scores.stride() != labels.stride():
+        raise ValueError("eval_ap_sorted: scores and labels [T][ld] of one layout expected")
+    _eval_dev(scores, torch.float32, "scores")
+    _eval_dev(labels, torch.float32, "labels")
+    _eval_dev(ap, torch.float64, "ap")
+    _eval_dev(valid, torch.uint8, "valid")
+    T, ld = scores.shape
+    if ap.numel() < T or valid.numel() < T:
+        raise ValueError("eval_ap_sorted: ap and valid hold fewer than T elements")
+    _lib.launch("gt_eval_ap_sorted", _ptr(scores), _ptr(labels), T, n, ld, _ptr(ap), _ptr(valid), _stream())
+
+
+# ------------------------------------------------------------------------------------------------
 # per-tower linears (PNAConv's pre_nns / post_nns): column slices in, column slices out
 # ------------------------------------------------------------------------------------------------
 class _TowerLinear(torch.autograd.Function):

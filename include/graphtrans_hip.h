@@ -806,6 +806,46 @@ int gt_bce_masked_bwd(const float* logits, const float* target, const float* out
                       int64_t T, int64_t ld, int64_t target_ld, float* dlogits, gt_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * Evaluation metrics on the device (csrc/metrics.hip): what the reference's `eval` computes on the host per batch
+ * (dataset/code.py:49-78 F1, dataset/mol.py:36-58 AP, dataset/tud.py:33-43 accuracy).  No atomics; every sum has a fixed
+ * order, two runs are bit-identical; nothing synchronises.
+ *
+ * gt_eval_argmax: pred[b][h] (int32 [B][H]) = argmax_c logits[b * ld + h * head_stride + c], c in [0, C), fp32 logits at any
+ *   4-byte aligned address.  torch.argmax's rule: the first maximum in column order; NaN counts as the maximum and the first
+ *   NaN wins; -0 == +0; a row of -inf gives 0.  One wave per row up to C = 1024, one block above; 16-byte loads between a
+ *   row's first and last 16-byte boundary, whatever ld, head_stride and the base are.  H > 16 or C < 1: GT_ERR_UNSUPPORTED.
+ *
+ * gt_eval_seq_f1 (Code2): per graph b, the prediction pred[b][0..H) cut at the first id C - 1 (__EOS__) and made a set; id
+ *   C - 2 (__UNK__) is a predicted word that matches nothing.  The reference set of graph g = graph_ids[b] (device int64, the
+ *   ids gt_collate takes; NULL: g = b) is ref_ids[g][0..R) (int32, distinct ids < C - 2, padded with -1) and counts n_ref[g]
+ *   words (the distinct words of the raw label, out-of-vocabulary ones included).  In float64: tp = |pred & ref|,
+ *   fp = |pred| - tp, fn = n_ref - tp, precision = tp / (tp + fp), recall = tp / (tp + fn), F1 = 2 p r / (p + r), each 0 where
+ *   its denominator is 0; written to rows[row_off + b][0..3).  A g outside [0, G) writes NaN.  rows_cap = rows the buffer
+ *   holds (row_off + B above it: GT_ERR_INVALID_ARG).  H > 16 or R > 64: GT_ERR_UNSUPPORTED.
+ *
+ * gt_eval_rows_mean_f64: out[0..3) = the column means of rows[0..n)[3], float64; the order of the additions depends on n alone,
+ *   not on how the rows were written.
+ *
+ * gt_eval_count_correct (TU accuracy): count[0] (device int64) += #{b < B : pred[b] == y[b]}, pred int32 (gt_eval_argmax with
+ *   H = 1), y int64.  One writer per launch: launches on one stream accumulate exactly.
+ *
+ * gt_eval_ap_sorted (Molpcba): task t (one block each) has n scores scores[t * ld + i], fp32, sorted descending, and their labels
+ *   labels[t * ld + i] in the same order: NaN = unlabelled (skipped wherever it stands), 1 = positive, anything else negative.
+ *   ap[t] (float64) = sum over thresholds of (recall_i - recall_{i-1}) * precision_i as scikit-learn's average_precision_score
+ *   over the labelled entries (one threshold per distinct score, tied scores together).  valid[t] (uint8) = 1 when the labelled
+ *   entries hold a positive and a negative (the OGB rule), else 0 and ap[t] = 0; 2 (and ap[t] = 0) when a labelled entry's score
+ *   is NaN -- scores must be finite, the caller raises on it. */
+int gt_eval_argmax(const float* logits, int64_t B, int64_t H, int64_t C, int64_t ld, int64_t head_stride, int32_t* pred,
+                   gt_stream_t stream);
+int gt_eval_seq_f1(const int32_t* pred, int64_t B, int64_t H, int64_t C, const int32_t* ref_ids, const int32_t* n_ref,
+                   int64_t R, int64_t G, const int64_t* graph_ids /* or NULL */, double* rows, int64_t row_off,
+                   int64_t rows_cap, gt_stream_t stream);
+int gt_eval_rows_mean_f64(const double* rows, int64_t n, double* out, gt_stream_t stream);
+int gt_eval_count_correct(const int32_t* pred, const int64_t* y, int64_t B, int64_t* count, gt_stream_t stream);
+int gt_eval_ap_sorted(const float* scores, const float* labels, int64_t T, int64_t n, int64_t ld, double* ap, uint8_t* valid,
+                      gt_stream_t stream);
+
+/* ---------------------------------------------------------------------------------------------
  * Composite layer entry points: ONE call enqueues every kernel of a layer's forward or backward
  * (the gt_* primitives above, in order, on `stream`).  Purpose: host cost — a training step is
  * ~500 kernel launches; issued from C back to back instead of through per-op Python/autograd
