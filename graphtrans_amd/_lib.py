@@ -174,6 +174,8 @@ SIGNATURES = {
     "gt_eval_rows_mean_f64": (_i, [_p, _i64, _p, _p]),
     "gt_eval_count_correct": (_i, [_p, _p, _i64, _p, _p]),
     "gt_eval_ap_sorted": (_i, [_p, _p, _i64, _i64, _i64, _p, _p, _p]),
+    "gt_eval_rows_sum_f64": (_i, [_p, _i64, _p, _p]),
+    "gt_eval_auc_sorted": (_i, [_p, _p, _i64, _i64, _i64, _p, _p, _p]),
     "gt_linear_bwd_workspace_bytes": (_sz, [_i, _i64, _i64, _i64]),
     "gt_linear_bwd": (_i, [_i, _i, _i, _p, _p, _p, _p, _p, _p, _p, _p, _p, _i64, _i64, _i64, _f, _p, _sz, _p]),
     # composite layers (descriptor structs are passed by pointer; see graphtrans_amd/layers.py)

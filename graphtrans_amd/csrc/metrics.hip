@@ -6,9 +6,10 @@
 // synchronisation of a pass is the read of the final numbers:
 //   k_argmax_block / k_argmax_wave : pred[b][h] = argmax of head h's C logits (torch.argmax's rule)   -- the hot kernel, HBM-bound
 //   k_seq_f1                       : per graph: decode at __EOS__, set precision / recall / F1 in float64 (the OGB F1 evaluator)
-//   k_rows_mean                    : mean of the per-graph rows, float64, fixed order
+//   k_rows_mean                    : mean (or plain sum) of the per-graph rows, float64, fixed order
 //   k_count_correct                : count += #{pred == y}                                          (TU accuracy)
 //   k_ap_sorted                    : average precision of one task per block over its scores sorted descending (Molpcba AP)
+//   k_auc_sorted                   : ROC-AUC of one task per block over the same sorted table, in integers (Molhiv ROC-AUC)
 // No kernel uses an atomic; every sum has a fixed order, so two runs are bit-identical.
 #include "gt_common.h"
 
@@ -107,6 +108,15 @@ __device__ __forceinline__ int blk_sum_int(int v, int* red) {
   __syncthreads();
   return v;
 }
+__device__ __forceinline__ int64_t blk_sum_i64(int64_t v, int64_t* red) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) v += (int64_t)__shfl_xor((long long)v, o, 64);
+  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
+  __syncthreads();
+  v = (red[0] + red[1]) + (red[2] + red[3]);
+  __syncthreads();
+  return v;
+}
 __device__ __forceinline__ double blk_sum_f64(double v, double* red) {   // a fixed tree: the same bits in every thread, every run
 #pragma unroll
   for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
@@ -181,7 +191,9 @@ __global__ void __launch_bounds__(MT) k_seq_f1(const int32_t* __restrict__ pred,
   o[2] = f1;
 }
 
-// out[k] = (sum_i rows[i][k]) / n: thread t adds rows t, t + MT, ... in order, then the fixed tree; depends on n alone
+// out[k] = (sum_i rows[i][k]) / n: thread t adds rows t, t + MT, ... in order, then the fixed tree; depends on n alone.
+// MEAN = false leaves the division out: the sums that ranks exchange (a mean of means is not the mean).
+template <bool MEAN>
 __global__ void __launch_bounds__(MT) k_rows_mean(const double* __restrict__ rows, int64_t n, double* __restrict__ out) {
   __shared__ double red[MT / 64];
   double s0 = 0.0, s1 = 0.0, s2 = 0.0;
@@ -194,9 +206,9 @@ __global__ void __launch_bounds__(MT) k_rows_mean(const double* __restrict__ row
   s1 = blk_sum_f64(s1, red);
   s2 = blk_sum_f64(s2, red);
   if (threadIdx.x == 0) {
-    out[0] = s0 / (double)n;
-    out[1] = s1 / (double)n;
-    out[2] = s2 / (double)n;
+    out[0] = MEAN ? s0 / (double)n : s0;
+    out[1] = MEAN ? s1 / (double)n : s1;
+    out[2] = MEAN ? s2 / (double)n : s2;
   }
 }
 
@@ -276,6 +288,68 @@ __global__ void __launch_bounds__(MT) k_ap_sorted(const float* __restrict__ scor
   }
 }
 
+// ---- Molhiv: ROC-AUC of one task per block ----------------------------------------------------------------------------------
+// The table of k_ap_sorted.  With tp_e, fp_e the labelled positives / negatives among entries 0..e at the end e of a run of equal
+// scores and tp_e', fp_e' the same at the run end before it (0 before the first), the trapezoids of scikit-learn's roc_auc_score are
+//   AUC = num / (2 P N),   num = sum over run ends e of (fp_e - fp_e') * (tp_e + tp_e')
+// an integer below n^2 / 2 < 2^61, kept in int64 (it passes 2^32 at n = 100 000).  A run without a labelled negative adds nothing,
+// so unlabelled entries may stand anywhere.  tp and fp never fall, so their values at the previous run end are running maxima over
+// the run ends before i: two max scans, carried from chunk to chunk like the + scan's totals -- a tie run over any number of chunk
+// borders is one threshold.  The one floating-point operation is the division: for 2 P N < 2^53 the correctly rounded quotient.
+__global__ void __launch_bounds__(MT) k_auc_sorted(const float* __restrict__ scores, const float* __restrict__ labels, int64_t n,
+                                                   int64_t ld, double* __restrict__ auc, uint8_t* __restrict__ valid) {
+  __shared__ int red[MT / 64];
+  __shared__ int64_t redl[MT / 64];
+  const int64_t t = blockIdx.x;
+  const float* __restrict__ sc = scores + t * ld;
+  const float* __restrict__ lb = labels + t * ld;
+  int pos = 0, neg = 0, bad = 0;
+  for (int64_t i = threadIdx.x; i < n; i += MT) {
+    const float y = lb[i], s = sc[i];
+    if (y == y) {
+      pos += y == 1.f ? 1 : 0;
+      neg += y == 1.f ? 0 : 1;
+      bad += s != s ? 1 : 0;
+    }
+  }
+  const int P = blk_sum_int(pos, red), N = blk_sum_int(neg, red);
+  bad = blk_sum_int(bad, red);
+  if (bad || P == 0 || N == 0) {   // the same in every thread
+    if (threadIdx.x == 0) {
+      auc[t] = 0.0;
+      valid[t] = bad ? 2 : 0;   // 2: a labelled entry has a NaN score
+    }
+    return;
+  }
+  int tp_c = 0, fp_c = 0, mt_c = 0, mf_c = 0;
+  int64_t num = 0;   // this thread's terms; one block sum behind the walk
+  for (int64_t base = 0; base < n; base += MT) {
+    const int64_t i = base + threadIdx.x;
+    const bool in = i < n;
+    const float s = in ? sc[i] : 0.f;
+    const float y = in ? lb[i] : 0.f;
+    const bool lab = in && y == y, p1 = lab && y == 1.f, n1 = lab && !p1;
+    const bool end = in && (i == n - 1 || sc[i + 1] != s);
+    int inc, exc, tot;
+    blk_scan<false>((p1 ? 1 : 0) | (n1 ? 1 << 16 : 0), red, inc, exc, tot);   // a chunk holds at most 256 of either
+    const int tp = tp_c + (inc & 0xffff), fp = fp_c + (inc >> 16);
+    int tinc, texc, ttot, finc, fexc, ftot;
+    blk_scan<true>(end ? tp : 0, red, tinc, texc, ttot);
+    blk_scan<true>(end ? fp : 0, red, finc, fexc, ftot);
+    const int tp_prev = mt_c > texc ? mt_c : texc, fp_prev = mf_c > fexc ? mf_c : fexc;
+    if (end) num += (int64_t)(fp - fp_prev) * (int64_t)(tp + tp_prev);
+    tp_c += tot & 0xffff;
+    fp_c += tot >> 16;
+    mt_c = mt_c > ttot ? mt_c : ttot;
+    mf_c = mf_c > ftot ? mf_c : ftot;
+  }
+  num = blk_sum_i64(num, redl);
+  if (threadIdx.x == 0) {
+    auc[t] = (double)num / (double)(2 * (int64_t)P * (int64_t)N);
+    valid[t] = 1;
+  }
+}
+
 }  // namespace
 
 extern "C" int gt_eval_argmax(const float* logits, int64_t B, int64_t H, int64_t C, int64_t ld, int64_t head_stride,
@@ -320,7 +394,15 @@ extern "C" int gt_eval_seq_f1(const int32_t* pred, int64_t B, int64_t H, int64_t
 extern "C" int gt_eval_rows_mean_f64(const double* rows, int64_t n, double* out, gt_stream_t stream_) {
   GT_CHECK_ARG(n > 0, "no rows");
   GT_CHECK_ARG(rows && out, "null buffer");
-  hipLaunchKernelGGL(k_rows_mean, dim3(1), dim3(MT), 0, (hipStream_t)stream_, rows, n, out);
+  hipLaunchKernelGGL(k_rows_mean<true>, dim3(1), dim3(MT), 0, (hipStream_t)stream_, rows, n, out);
+  GT_CHECK_LAUNCH();
+  return GT_OK;
+}
+
+extern "C" int gt_eval_rows_sum_f64(const double* rows, int64_t n, double* out, gt_stream_t stream_) {
+  GT_CHECK_ARG(n > 0, "no rows");
+  GT_CHECK_ARG(rows && out, "null buffer");
+  hipLaunchKernelGGL(k_rows_mean<false>, dim3(1), dim3(MT), 0, (hipStream_t)stream_, rows, n, out);
   GT_CHECK_LAUNCH();
   return GT_OK;
 }
@@ -339,6 +421,16 @@ extern "C" int gt_eval_ap_sorted(const float* scores, const float* labels, int64
   GT_CHECK_ARG(scores && labels && ap && valid, "null buffer");
   GtProfScope prof__(GT_PROF_NORM, "gt_eval_ap_sorted", stream_, {T, n});
   hipLaunchKernelGGL(k_ap_sorted, dim3((unsigned)T), dim3(MT), 0, (hipStream_t)stream_, scores, labels, n, ld, ap, valid);
+  GT_CHECK_LAUNCH();
+  return GT_OK;
+}
+
+extern "C" int gt_eval_auc_sorted(const float* scores, const float* labels, int64_t T, int64_t n, int64_t ld, double* auc,
+                                  uint8_t* valid, gt_stream_t stream_) {
+  GT_CHECK_ARG(T > 0 && T < INT32_MAX && n > 0 && n < INT32_MAX && ld >= n, "bad sizes");
+  GT_CHECK_ARG(scores && labels && auc && valid, "null buffer");
+  GtProfScope prof__(GT_PROF_NORM, "gt_eval_auc_sorted", stream_, {T, n});
+  hipLaunchKernelGGL(k_auc_sorted, dim3((unsigned)T), dim3(MT), 0, (hipStream_t)stream_, scores, labels, n, ld, auc, valid);
   GT_CHECK_LAUNCH();
   return GT_OK;
 }

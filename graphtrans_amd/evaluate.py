@@ -5,8 +5,15 @@ dataset/tud.py:33-43) and the OGB evaluators behind them (F1 for ogbg-code2, AP 
     result = evaluate(model, store.batches(256, ids=split), ev)      # {"precision": .., "recall": .., "F1": ..}
 
 `update` only enqueues kernels on the current stream (no `.item()`, no `.cpu()`, no boolean indexing, no allocation: every
-buffer is made in the constructor for `num_graphs` graphs); `result()` holds the one synchronisation of a pass.  Each process
-evaluates the batches it is given: there is no reduction across data-parallel ranks here.
+buffer is made in the constructor for `num_graphs` graphs); `result()` holds the one synchronisation of a pass.
+
+`result()` speaks of the batches this process was given, whether or not torch.distributed is initialised.  `result(group)` (and
+`evaluate(..., group=group)`) is collective over a process group: every rank calls it and every rank receives the dict that one
+evaluator fed all the ranks' shards in rank order would return.  F1 exchanges float64 column sums and counts, accuracy two
+integers; AP and ROC-AUC are rank statistics, so the ranks' score and label columns are gathered into the one table and every
+rank sorts it (bit-identical to the single process).  Tensors travel as `ops._dist_reduce` sends them: on the device over
+nccl, through the host elsewhere.  The gathered table's width is a host number, so `MolAP` / `MolRocAuc` exchange their counts
+before the columns: that is a second read on nccl; through the host every exchange is one.
 """
 import numpy as np
 import torch
@@ -95,6 +102,13 @@ class _Evaluator:
             raise ValueError(f"more than num_graphs = {self.num_graphs} graphs in one evaluation pass")
 
 
+def _gather_counts(n, group, device):
+    """every rank's host count as a list in rank order (`ops._dist_reduce`: a device tensor on nccl, a host tensor elsewhere)"""
+    import torch.distributed as dist
+    where = device if dist.get_backend(group) == "nccl" else "cpu"
+    return ops._dist_reduce(torch.tensor([n], dtype=torch.int64, device=where), group, gather=True).view(-1).tolist()
+
+
 class Code2F1(_Evaluator):
     """ogbg-code2's metric (the OGB "F1" evaluator over decoded word sets): mean precision, recall and F1 over the graphs seen.
     ref_ids / n_ref: `encode_code2_refs` of the split; `graph_ids` of `update` index them (None: the batches walk the split in
@@ -138,16 +152,35 @@ class Code2F1(_Evaluator):
         self.seen += B
         self.cursor += B
 
-    def result(self):
+    def result(self, group=None):
+        if group is not None:
+            return self._result_ranks(group)
         if self.seen == 0:
             raise RuntimeError("Code2F1.result(): no graph was evaluated")
         p, r, f = ops.eval_rows_mean(self.rows, self.seen, self.out).tolist()   # the one synchronisation
         return {"precision": p, "recall": r, "F1": f}
 
+    def _result_ranks(self, group):
+        """the mean over every rank's graphs: the local column sums and the count travel, the ranks' sums are added in rank order
+        in float64 and divided once (a mean of the ranks' means would weigh a short shard like a long one)"""
+        packed = torch.zeros(4, dtype=torch.float64, device=self.device)   # a rank that saw nothing sends zeros
+        if self.seen:
+            ops.eval_rows_sum(self.rows, self.seen, packed)
+            packed[3:].fill_(float(self.seen))
+        every = ops._dist_reduce(packed, group, gather=True).tolist()       # the one synchronisation
+        sums, n = [0.0, 0.0, 0.0], 0
+        for s0, s1, s2, count in every:
+            sums = [sums[0] + s0, sums[1] + s1, sums[2] + s2]
+            n += int(count)
+        if n == 0:
+            raise RuntimeError("Code2F1.result(): no graph was evaluated on any rank")
+        return {"precision": sums[0] / n, "recall": sums[1] / n, "F1": sums[2] / n}
 
-class MolAP(_Evaluator):
-    """ogbg-molpcba's metric (the OGB "ap" evaluator): scikit-learn's average_precision_score per task over its labelled graphs,
-    averaged over the tasks whose labels hold a positive and a negative.  Scores must be finite."""
+
+class _MolRanked(_Evaluator):
+    """The rank statistics of the molecule datasets: the (task, graph) score and label tables, their sort and the gather of the
+    labels behind it; a subclass names the kernel over the sorted table and the key of its result."""
+    KEY = KERNEL = WHAT = None
 
     def __init__(self, num_graphs, num_tasks, device="cuda"):
         super().__init__(num_graphs, device)
@@ -155,38 +188,77 @@ class MolAP(_Evaluator):
         kw = dict(device=self.device)
         self.scores = torch.empty(self.T, self.num_graphs, dtype=torch.float32, **kw)   # task major: a task's scores are one row
         self.labels = torch.empty(self.T, self.num_graphs, dtype=torch.float32, **kw)
-        self.ap = torch.empty(self.T, dtype=torch.float64, **kw)
+        self.value = torch.empty(self.T, dtype=torch.float64, **kw)
         self.valid = torch.empty(self.T, dtype=torch.uint8, **kw)
 
     def reset(self):
         self.seen = 0
 
     def update(self, pred, batch, graph_ids=None):
+        name = type(self).__name__
         y = batch.y if hasattr(batch, "y") else batch
         if not (isinstance(pred, torch.Tensor) and pred.is_cuda and y.is_cuda):
             raise RuntimeError("graphtrans_amd.evaluate runs on the GPU only (no CPU fallback)")
         B = pred.shape[0]
         if pred.dim() != 2 or pred.shape[1] != self.T or y.numel() != B * self.T:
-            raise ValueError(f"MolAP: (B, {self.T}) logits and labels expected")
+            raise ValueError(f"{name}: (B, {self.T}) logits and labels expected")
         self._room(B)
         cols = slice(self.seen, self.seen + B)
         self.scores[:, cols].copy_(pred.t())                 # strided device copies (with the cast, if any) into the column range
         self.labels[:, cols].copy_(y.view(B, self.T).t())
         self.seen += B
 
-    def result(self):
+    def _table(self, group):
+        """(scores, labels, n): this process's [T][seen] tables, or with a group the ranks' tables side by side in rank order --
+        the table one evaluator fed every rank's shard in that order holds, so the sort and the kernel give the same bits"""
         n = self.seen
+        if group is None:
+            return self.scores[:, :n], self.labels[:, :n], n
+        counts = _gather_counts(n, group, self.device)
+        width = max(counts)
+        if width == 0:
+            return None, None, 0
+        wire = torch.zeros(2, self.T, width, dtype=torch.float32, device=self.device)   # padded to the largest count on the wire
+        wire[0, :, :n].copy_(self.scores[:, :n])
+        wire[1, :, :n].copy_(self.labels[:, :n])
+        every = ops._dist_reduce(wire, group, gather=True)                               # (world, 2, T, width)
+        both = torch.cat([every[r, :, :, :c] for r, c in enumerate(counts)], 2)
+        return both[0], both[1], sum(counts)
+
+    def result(self, group=None):
+        name = type(self).__name__
+        scores, labels, n = self._table(group)
         if n == 0:
-            raise RuntimeError("MolAP.result(): no graph was evaluated")
-        s, order = torch.sort(self.scores[:, :n], dim=1, descending=True, stable=True)
-        lab = torch.gather(self.labels[:, :n], 1, order)
-        ops.eval_ap_sorted(s, lab, n, self.ap, self.valid)
-        ap, valid = torch.cat([self.ap, self.valid.to(torch.float64)]).cpu().view(2, self.T).numpy()   # the one synchronisation
+            raise RuntimeError(f"{name}.result(): no graph was evaluated")
+        s, order = torch.sort(scores, dim=1, descending=True, stable=True)
+        lab = torch.gather(labels, 1, order)
+        type(self).KERNEL(s, lab, n, self.value, self.valid)
+        value, valid = torch.cat([self.value, self.valid.to(torch.float64)]).cpu().view(2, self.T).numpy()   # the one synchronisation
         if (valid == 2).any():
-            raise RuntimeError(f"MolAP: NaN scores on labelled entries of {int((valid == 2).sum())} task(s); scores must be finite")
+            raise RuntimeError(f"{name}: NaN scores on labelled entries of {int((valid == 2).sum())} task(s); scores must be finite")
         if not (valid == 1).any():
-            raise RuntimeError("No positively labeled data available. Cannot compute Average Precision.")
-        return {"ap": float(ap[valid == 1].sum() / (valid == 1).sum())}
+            raise RuntimeError(f"No positively labeled data available. Cannot compute {self.WHAT}.")
+        return {self.KEY: float(value[valid == 1].sum() / (valid == 1).sum())}
+
+
+class MolAP(_MolRanked):
+    """ogbg-molpcba's metric (the OGB "ap" evaluator): scikit-learn's average_precision_score per task over its labelled graphs,
+    averaged over the tasks whose labels hold a positive and a negative.  Scores must be finite."""
+    KEY, KERNEL, WHAT = "ap", staticmethod(ops.eval_ap_sorted), "Average Precision"
+
+
+class MolRocAuc(_MolRanked):
+    """ogbg-molhiv's metric (the OGB "rocauc" evaluator): scikit-learn's roc_auc_score per task over its labelled graphs, averaged
+    over the tasks whose labels hold a positive and a negative.  Scores must be finite."""
+    KEY, KERNEL, WHAT = "rocauc", staticmethod(ops.eval_auc_sorted), "ROC-AUC"
+
+
+def mol_evaluator(eval_metric, num_graphs, num_tasks, device="cuda"):
+    """The evaluator of a molecule dataset by the reference's `dataset.eval_metric`: "ap" (ogbg-molpcba) or "rocauc" (ogbg-molhiv)"""
+    kinds = {"ap": MolAP, "rocauc": MolRocAuc}
+    if eval_metric not in kinds:
+        raise ValueError(f"mol_evaluator: eval_metric {eval_metric!r} is not one of {sorted(kinds)}")
+    return kinds[eval_metric](num_graphs, num_tasks, device)
 
 
 class TudAccuracy(_Evaluator):
@@ -212,15 +284,23 @@ class TudAccuracy(_Evaluator):
         ops.eval_count_correct(p, y.reshape(-1), B, self.count)
         self.seen += B
 
-    def result(self):
-        return {"acc": int(self.count.item()) / self.num_graphs}   # the one synchronisation
+    def result(self, group=None):
+        if group is None:
+            return {"acc": int(self.count.item()) / self.num_graphs}   # the one synchronisation
+        both = torch.empty(2, dtype=torch.int64, device=self.device)
+        both[:1].copy_(self.count)
+        both[1:].fill_(self.num_graphs)
+        correct, graphs = ops._dist_reduce(both, group, gather=False).tolist()   # the one synchronisation
+        return {"acc": correct / graphs}
 
 
-def evaluate(model, batches, evaluator, skip_single_node=None):
+def evaluate(model, batches, evaluator, skip_single_node=None, group=None):
     """One evaluation pass, the loop of dataset/*.py: model.eval(), torch.no_grad(), every batch through `evaluator.update`,
     training mode restored on exit.  A batch whose x has one row is skipped as the Code2 and Molpcba loops do
     (dataset/code.py:57, dataset/mol.py:44); the TU loop does not skip (`skip_single_node` overrides the choice by evaluator).
-    Batches made by `GraphStore.collate` carry their graph ids, which `Code2F1` uses to find the reference sets."""
+    Batches made by `GraphStore.collate` carry their graph ids, which `Code2F1` uses to find the reference sets.
+    With a process group (`batches` being this rank's shard, e.g. `store.batches(256, ids=split[rank::world])`) the call is
+    collective and returns on every rank what `evaluator.result(group)` says: the result over all the ranks' shards."""
     if skip_single_node is None:
         skip_single_node = not isinstance(evaluator, TudAccuracy)
     was_training = model.training
@@ -235,4 +315,4 @@ def evaluate(model, batches, evaluator, skip_single_node=None):
                 evaluator.update(model(batch), batch, getattr(batch, "_graph_ids", None))
     finally:
         model.train(was_training)
-    return evaluator.result()
+    return evaluator.result() if group is None else evaluator.result(group)

@@ -1073,10 +1073,15 @@ def eval_count_correct(pred, y, B, count):
     _lib.launch("gt_eval_count_correct", _ptr(pred), _ptr(y), B, _ptr(count), _stream())
 
 
+def _eval_table(scores, labels, name):
+    """scores and labels as [T][ld] tables of one layout (the pitch of a single row is no layout: T = 1 has none to compare)"""
+    if scores.dim() != 2 or scores.shape != labels.shape or (scores.shape[0] > 1 and scores.stride() != labels.stride()):
+        raise ValueError(f"{name}: scores and labels [T][ld] of one layout expected")
+
+
 def eval_ap_sorted(scores, labels, n, ap, valid):
     """ap[t], valid[t] of every task t: scores [T][ld >= n] fp32 sorted descending along dim 1, labels in the same order"""
-    if scores.dim() != 2 or scores.shape != labels.shape or scores.stride() != labels.stride():
-        raise ValueError("eval_ap_sorted: scores and labels [T][ld] of one layout expected")
+    _eval_table(scores, labels, "eval_ap_sorted")
     _eval_dev(scores, torch.float32, "scores")
     _eval_dev(labels, torch.float32, "labels")
     _eval_dev(ap, torch.float64, "ap")
@@ -1085,6 +1090,29 @@ def eval_ap_sorted(scores, labels, n, ap, valid):
     if ap.numel() < T or valid.numel() < T:
         raise ValueError("eval_ap_sorted: ap and valid hold fewer than T elements")
     _lib.launch("gt_eval_ap_sorted", _ptr(scores), _ptr(labels), T, n, ld, _ptr(ap), _ptr(valid), _stream())
+
+
+def eval_auc_sorted(scores, labels, n, auc, valid):
+    """auc[t] (ROC-AUC), valid[t] of every task t: the table of `eval_ap_sorted`"""
+    _eval_table(scores, labels, "eval_auc_sorted")
+    _eval_dev(scores, torch.float32, "scores")
+    _eval_dev(labels, torch.float32, "labels")
+    _eval_dev(auc, torch.float64, "auc")
+    _eval_dev(valid, torch.uint8, "valid")
+    T, ld = scores.shape
+    if auc.numel() < T or valid.numel() < T:
+        raise ValueError("eval_auc_sorted: auc and valid hold fewer than T elements")
+    _lib.launch("gt_eval_auc_sorted", _ptr(scores), _ptr(labels), T, n, ld, _ptr(auc), _ptr(valid), _stream())
+
+
+def eval_rows_sum(rows, n, out):
+    """out[0..3) = column sums of rows[0..n), float64: `eval_rows_mean` without the division, the same additions"""
+    _eval_dev(rows, torch.float64, "rows")
+    _eval_dev(out, torch.float64, "out")
+    if rows.dim() != 2 or rows.shape[1] != 3 or not 0 < n <= rows.shape[0] or out.numel() < 3:
+        raise ValueError("eval_rows_sum: rows [>= n][3] with n >= 1 and out [3] expected")
+    _lib.launch("gt_eval_rows_sum_f64", _ptr(rows), n, _ptr(out), _stream())
+    return out
 
 
 # ------------------------------------------------------------------------------------------------

@@ -834,7 +834,16 @@ int gt_bce_masked_bwd(const float* logits, const float* target, const float* out
  *   ap[t] (float64) = sum over thresholds of (recall_i - recall_{i-1}) * precision_i as scikit-learn's average_precision_score
  *   over the labelled entries (one threshold per distinct score, tied scores together).  valid[t] (uint8) = 1 when the labelled
  *   entries hold a positive and a negative (the OGB rule), else 0 and ap[t] = 0; 2 (and ap[t] = 0) when a labelled entry's score
- *   is NaN -- scores must be finite, the caller raises on it. */
+ *   is NaN -- scores must be finite, the caller raises on it.
+ *
+ * gt_eval_rows_sum_f64: gt_eval_rows_mean_f64 without the division: out[0..3) = the column sums of rows[0..n)[3], the same
+ *   additions in the same order (what data-parallel ranks exchange: a mean of means is not the mean).
+ *
+ * gt_eval_auc_sorted (Molhiv): the table, the labels and valid[t] of gt_eval_ap_sorted.  auc[t] (float64) = scikit-learn's
+ *   roc_auc_score over the labelled entries: with tp_e, fp_e the labelled positives / negatives among entries 0..e at the end e of
+ *   a run of equal scores (runs over all entries) and tp_e', fp_e' those at the run end before it (0 before the first),
+ *   num = sum_e (fp_e - fp_e') * (tp_e + tp_e') in int64 and auc[t] = (double)num / (double)(2 P N): the one rounding, so for
+ *   2 P N < 2^53 the correctly rounded quotient.  auc[t] = 0 unless valid[t] == 1. */
 int gt_eval_argmax(const float* logits, int64_t B, int64_t H, int64_t C, int64_t ld, int64_t head_stride, int32_t* pred,
                    gt_stream_t stream);
 int gt_eval_seq_f1(const int32_t* pred, int64_t B, int64_t H, int64_t C, const int32_t* ref_ids, const int32_t* n_ref,
@@ -844,6 +853,9 @@ int gt_eval_rows_mean_f64(const double* rows, int64_t n, double* out, gt_stream_
 int gt_eval_count_correct(const int32_t* pred, const int64_t* y, int64_t B, int64_t* count, gt_stream_t stream);
 int gt_eval_ap_sorted(const float* scores, const float* labels, int64_t T, int64_t n, int64_t ld, double* ap, uint8_t* valid,
                       gt_stream_t stream);
+int gt_eval_rows_sum_f64(const double* rows, int64_t n, double* out, gt_stream_t stream);
+int gt_eval_auc_sorted(const float* scores, const float* labels, int64_t T, int64_t n, int64_t ld, double* auc, uint8_t* valid,
+                       gt_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------------
  * Composite layer entry points: ONE call enqueues every kernel of a layer's forward or backward

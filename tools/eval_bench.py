@@ -3,9 +3,11 @@
             every forward, `result()` synchronises once (gt_eval_rows_mean_f64; torch.sort + gt_eval_ap_sorted)
   host      the reference's loop, written out below: torch.argmax per head + torch.cat + a `.cpu()` per graph + Python sets per graph
             (Code2); `.cpu()` of every batch of logits and one scikit-learn average_precision_score per task (Molpcba; the numpy
-            statement of tests/eval_refs.py stands in where scikit-learn does not import, and the line says so)
-Rows: code2 (bench.py's Code2 model, 5 heads of 5002 logits) and molpcba (128 tasks), `--batches` batches of `--batch` graphs each,
-generated once and kept on the device; the label sets are random words of the vocabulary plus out-of-vocabulary words.
+            statement of tests/eval_refs.py stands in where scikit-learn does not import, and the line says so); the same loop with
+            roc_auc_score (Molhiv; tests/eval_auc_refs.py stands in)
+Rows: code2 (bench.py's Code2 model, 5 heads of 5002 logits), molpcba (128 tasks) and molhiv (the Molpcba model with one task, about
+3.5 % positives and a few unlabelled graphs, scored by `MolRocAuc`: torch.sort + gt_eval_auc_sorted), `--batches` batches of `--batch`
+graphs each, generated once and kept on the device; the label sets are random words of the vocabulary plus out-of-vocabulary words.
 Per row, one JSON line (wall times of a whole pass in ms, each the median of `--reps` passes, device drained at the end of each):
   forward_ms        model.eval() forwards alone
   device_pass_ms    evaluate(model, batches, evaluator): forwards + metric
@@ -13,9 +15,9 @@ Per row, one JSON line (wall times of a whole pass in ms, each the median of `--
   device_metric_ms  the evaluator alone on logits kept from the forwards (update per batch + result), and
   host_metric_ms    the host loop alone on the same logits
   metric_kernel_ms  HIP-event time of the gt_eval_* launches of one pass (sum), and `metric_share` = that over forward_ms
-  equal             the two ways agree: F1 rows bit for bit, AP within (n + 8) * 2^-52
+  equal             the two ways agree: F1 rows bit for bit, AP and ROC-AUC within (n + 8) * 2^-52
 
-    python tools/eval_bench.py [--batches 16] [--batch 256] [--reps 5] [--rows code2,molpcba] [--mode mixed]
+    python tools/eval_bench.py [--batches 16] [--batch 256] [--reps 5] [--rows code2,molpcba,molhiv] [--mode mixed]
 """
 import argparse
 import json
@@ -80,8 +82,8 @@ def host_code2(outs, seqs, idx2vocab):
     return {"precision": float(np.average(rows[:, 0])), "recall": float(np.average(rows[:, 1])), "F1": float(np.average(rows[:, 2]))}, rows
 
 
-def host_mol(outs, batches, ap_score):
-    """dataset/mol.py:50-58 and the OGB ap evaluator"""
+def host_mol(outs, batches, ap_score, key="ap"):
+    """dataset/mol.py:50-58 and the OGB ap evaluator (or, with roc_auc_score for `ap_score`, its rocauc evaluator: the same loop)"""
     y_true = torch.cat([b.y.view(o.shape).detach().cpu() for b, o in zip(batches, outs)], 0).numpy()
     y_pred = torch.cat([o.detach().cpu() for o in outs], 0).numpy()
     aps = []
@@ -89,11 +91,31 @@ def host_mol(outs, batches, ap_score):
         if np.sum(y_true[:, i] == 1) > 0 and np.sum(y_true[:, i] == 0) > 0:
             lab = y_true[:, i] == y_true[:, i]
             aps.append(ap_score(y_true[lab, i], y_pred[lab, i]))
-    return {"ap": sum(aps) / len(aps)}
+    return {key: sum(aps) / len(aps)}
+
+
+def molhiv_row(tok, batch_graphs):
+    """bench.py's Molpcba model with one task; labels of about 3.5 % positives (ogbg-molhiv's share) and 1 % unlabelled"""
+    import bench
+    from graphtrans_amd import synth
+    from graphtrans_amd.encoders import AtomEncoder, BondEncoder
+    from graphtrans_amd.models.gnn_transformer import GNNTransformer
+    args = bench.model_args("molpcba", tok)
+    model = GNNTransformer(1, AtomEncoder(args.gnn_emb_dim), lambda d: BondEncoder(d), args).to("cuda:0")
+
+    def gen(seed):
+        b = synth.molpcba_like(B=batch_graphs, seed=seed, num_tasks=1)
+        g = torch.Generator().manual_seed(1000 + seed)
+        y = (torch.rand(batch_graphs, 1, generator=g) < 0.035).float()
+        y[torch.rand(batch_graphs, 1, generator=g) < 0.01] = float("nan")
+        b.y = y
+        return b
+    return model, gen
 
 
 def metric_kernel_ms(_lib, fn):
-    _lib.TIMER = timer = _lib.KernelTimer(["gt_eval_argmax", "gt_eval_seq_f1", "gt_eval_rows_mean_f64", "gt_eval_ap_sorted"])
+    _lib.TIMER = timer = _lib.KernelTimer(["gt_eval_argmax", "gt_eval_seq_f1", "gt_eval_rows_mean_f64", "gt_eval_ap_sorted",
+                                            "gt_eval_auc_sorted"])
     try:
         fn()
     finally:
@@ -106,14 +128,15 @@ def main():
     ap.add_argument("--batches", type=int, default=16)
     ap.add_argument("--batch", type=int, default=256)
     ap.add_argument("--reps", type=int, default=5)
-    ap.add_argument("--rows", default="code2,molpcba")
+    ap.add_argument("--rows", default="code2,molpcba,molhiv")
     ap.add_argument("--mode", default="mixed", choices=["mixed", "bf16", "fp32"])
     opt = ap.parse_args()
     assert torch.cuda.is_available(), "eval_bench needs a GPU"
     import bench
+    import eval_auc_refs
     import eval_refs
     from graphtrans_amd import _lib, ops
-    from graphtrans_amd.evaluate import Code2F1, MolAP, encode_code2_refs, evaluate
+    from graphtrans_amd.evaluate import Code2F1, MolAP, MolRocAuc, encode_code2_refs, evaluate
     matmul, tok = bench.MODES[opt.mode]
     ops.set_matmul_dtype(matmul)
     try:
@@ -122,16 +145,28 @@ def main():
     except ImportError:
         ap_score = lambda y, s: eval_refs.average_precision(s, y)[0]   # noqa: E731
         ap_name = "numpy statement (scikit-learn does not import)"
+    try:
+        from sklearn.metrics import roc_auc_score as auc_score
+    except ImportError:
+        def auc_score(y, s):
+            num, den, _ = eval_auc_refs.roc_auc(s, y)
+            return num / den
     G = opt.batches * opt.batch
     for row in opt.rows.split(","):
         torch.manual_seed(0)
-        _, model, gen, _, _ = bench.build(row, tok, "cuda:0", opt.batch)
+        if row == "molhiv":
+            model, gen = molhiv_row(tok, opt.batch)
+        else:
+            _, model, gen, _, _ = bench.build(row, tok, "cuda:0", opt.batch)
         batches = [gen(seed).to("cuda:0") for seed in range(opt.batches)]
         if row == "code2":
             vocab, seqs = code2_labels(G, 5002, 0)
             idx2vocab = {i: w for w, i in vocab.items()}
             ev = Code2F1(*encode_code2_refs(seqs, vocab), num_vocab=5002, max_seq_len=5, num_graphs=G)
             host = lambda outs: host_code2(outs, seqs, idx2vocab)[0]   # noqa: E731
+        elif row == "molhiv":
+            ev = MolRocAuc(num_graphs=G, num_tasks=1)
+            host = lambda outs: host_mol(outs, batches, auc_score, "rocauc")   # noqa: E731
         else:
             ev = MolAP(num_graphs=G, num_tasks=128)
             host = lambda outs: host_mol(outs, batches, ap_score)     # noqa: E731
@@ -152,7 +187,8 @@ def main():
         if row == "code2":
             equal = bool(np.array_equal(ev.rows[:ev.seen].cpu().numpy(), host_code2(outs, seqs, idx2vocab)[1]))
         else:
-            equal = bool(abs(res_dev["ap"] - res_host["ap"]) <= (G + 8) * 2.0 ** -52)
+            key = "rocauc" if row == "molhiv" else "ap"
+            equal = bool(abs(res_dev[key] - res_host[key]) <= (G + 8) * 2.0 ** -52)
         print(json.dumps(dict(row=row, mode=opt.mode, batches=opt.batches, batch=opt.batch, graphs=G, reps=opt.reps,
                               forward_ms=t_fwd, device_pass_ms=t_dev, host_pass_ms=t_host, device_metric_ms=t_dev_metric,
                               host_metric_ms=t_host_metric, metric_kernel_ms=kern,
