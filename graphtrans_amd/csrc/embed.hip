@@ -13,6 +13,10 @@
 // not depend on the arrival order): scale = 2^30 / max|g| (one abs-max pass), then one scatter pass
 // of int64 atomics (LDS slabs for the small tables, see k_embed_scatter) and one conversion pass.  Precision: 2^-30 relative to the largest gradient
 // element, i.e. the same order as an fp32 sum that contains that element.
+//
+// Token-row variants (gt_embed_tokens_fwd / _bwd; the plain Transformer model, models/transformer.py:87-101, whose token rows ARE the
+// encoder's rows): the forward writes node n's sum (+ the FLAG perturbation) to row rows[n] of the packed token matrix in the token
+// type, the sorted backward reads the token-row gradient through the same map -- no [N][D] node matrix in either direction.
 #include "gt_common.h"
 
 namespace {
@@ -55,6 +59,35 @@ __global__ void __launch_bounds__(ET) k_embed_fwd(EmbArgs a) {
     }
     if (a.add_before == a.T) s = gt_add4(s, *reinterpret_cast<const float4*>(a.add + n * a.D + c));
     *reinterpret_cast<float4*>(a.out + n * a.D + c) = s;
+  }
+}
+
+// The same sum written straight into the token matrix (the plain Transformer's input): node n's row goes to tokens[rows[n]], rows =
+// gt_seq_token_rows' map (-1: a leading node its truncated graph drops, neither read nor written).  The adds are k_embed_fwd's with
+// add_before == T (tables in order, the row operand last, fp32), then ONE rounding to the token type.
+template <typename T>
+__global__ void __launch_bounds__(ET) k_embed_tokens_fwd(EmbArgs a, const int32_t* __restrict__ rows, T* __restrict__ tokens) {
+  const int64_t C = a.D / 4, total = a.N * C;
+  for (int64_t i = (int64_t)blockIdx.x * ET + threadIdx.x; i < total; i += (int64_t)gridDim.x * ET) {
+    const int64_t n = i / C, c = (i % C) * 4;
+    const int64_t r = rows[n];
+    if (r < 0) continue;
+    float4 s = gt_zero4();
+    for (int t = 0; t < a.T; ++t) s = gt_add4(s, *reinterpret_cast<const float4*>(a.table[t] + emb_index(a, t, n) * a.D + c));
+    if (a.add) s = gt_add4(s, *reinterpret_cast<const float4*>(a.add + n * a.D + c));
+    gt_store4<T>(tokens + r * a.D + c, s);
+  }
+}
+
+// d_add[n] = float(d_tokens[rows[n]]), zero rows for the dropped nodes (the gradient of the row operand above)
+template <typename T>
+__global__ void __launch_bounds__(ET) k_embed_tokens_dadd(const T* __restrict__ d_tokens, const int32_t* __restrict__ rows, int64_t N,
+                                                          int64_t D, float* __restrict__ d_add) {
+  const int64_t C = D / 4, total = N * C;
+  for (int64_t i = (int64_t)blockIdx.x * ET + threadIdx.x; i < total; i += (int64_t)gridDim.x * ET) {
+    const int64_t n = i / C, c = (i % C) * 4;
+    const int64_t r = rows[n];
+    *reinterpret_cast<float4*>(d_add + n * D + c) = r >= 0 ? gt_load4<T>(d_tokens + r * D + c) : gt_zero4();
   }
 }
 
@@ -334,12 +367,27 @@ struct SegArgs {
   const int32_t* order;
   const int32_t* keys;
   const float* g;
+  const void* gtok;        // mapped source (k_eseg_reduce<SEG_SRC_TOK_*>): the gradient of node n is row rowmap[n] of gtok,
+  const int32_t* rowmap;   // 0 where rowmap[n] < 0
   float* dtable[MAX_TABLES];
   float* head;  // [T][nchunks][D]
   float* tail;  // [T][nchunks][D]
 };
 
+// the gradient operand of R1: node rows [N][D] fp32, or token rows (fp32 / bf16) read through the row map
+enum { SEG_SRC_NODES = 0, SEG_SRC_TOK_F32 = 1, SEG_SRC_TOK_BF16 = 2 };
+// `node`: the node id (SEG_SRC_NODES), else the node's token row, -1 for a dropped node
+template <int SRC>
+__device__ __forceinline__ float seg_grad(const SegArgs& a, int node, int64_t c) {
+  if (SRC == SEG_SRC_NODES) return a.g[(int64_t)node * a.D + c];
+  const int64_t r = node;
+  if (r < 0) return 0.f;
+  if (SRC == SEG_SRC_TOK_F32) return static_cast<const float*>(a.gtok)[r * a.D + c];
+  return gt_bf16_to_f32(static_cast<const gt_bf16*>(a.gtok)[r * a.D + c]);
+}
+
 // R1 (grid: nchunks x T)
+template <int SRC>
 __global__ void __launch_bounds__(SEG_T) k_eseg_reduce(SegArgs a) {
   const int t = blockIdx.y, ch = blockIdx.x;
   float* dt = a.dtable[t];
@@ -356,6 +404,13 @@ __global__ void __launch_bounds__(SEG_T) k_eseg_reduce(SegArgs a) {
   const bool after = (int64_t)bs[last_row + 1] > p1;            // last row continues in a later chunk
   float* head = a.head + ((int64_t)t * a.nchunks + ch) * a.D;
   float* tail = a.tail + ((int64_t)t * a.nchunks + ch) * a.D;
+  // mapped sources: the token rows of the chunk's positions once per block, so that the walk below stays a chain of two dependent
+  // loads (row id -> gradient) and not three (node id -> row map -> gradient)
+  __shared__ int32_t tok_row[SEG_CH];
+  if (SRC != SEG_SRC_NODES) {
+    if (threadIdx.x < p1 - p0) tok_row[threadIdx.x] = a.rowmap[ord[p0 + threadIdx.x]];
+    __syncthreads();   // (every return above is taken by the whole block)
+  }
   for (int64_t c = threadIdx.x; c < a.D; c += SEG_T) {
     int cur = first_row;
     float acc = 0.f;
@@ -371,11 +426,11 @@ __global__ void __launch_bounds__(SEG_T) k_eseg_reduce(SegArgs a) {
 #pragma unroll
       for (int u = 0; u < 8; ++u) {
         const bool ok = pb + u < p1;
-        node[u] = ok ? ord[pb + u] : 0;
+        node[u] = ok ? (SRC == SEG_SRC_NODES ? ord[pb + u] : tok_row[pb + u - p0]) : 0;
         row[u] = ok ? ks[pb + u] : -1;
       }
 #pragma unroll
-      for (int u = 0; u < 8; ++u) v[u] = row[u] >= 0 ? a.g[(int64_t)node[u] * a.D + c] : 0.f;
+      for (int u = 0; u < 8; ++u) v[u] = row[u] >= 0 ? seg_grad<SRC>(a, node[u], c) : 0.f;
 #pragma unroll
       for (int u = 0; u < 8; ++u) {
         if (row[u] < 0) continue;
@@ -587,17 +642,14 @@ extern "C" size_t gt_embed_sum_bwd_sorted_workspace_bytes(int num_tables, int64_
   return (size_t)2 * num_tables * gt_cdiv(N > 0 ? N : 1, SEG_CH) * D * sizeof(float) + 256;
 }
 
-extern "C" int gt_embed_sum_bwd_sorted(int num_tables, const int64_t* table_rows_host, const float* grad_out, int64_t N,
-                                       int64_t D, const void* plan, float* const* d_tables_host, void* workspace,
-                                       size_t workspace_bytes, gt_stream_t stream_) {
-  int rc = emb_check("gt_embed_sum_bwd_sorted", num_tables, N, D);
-  if (rc) return rc;
-  GT_CHECK_ARG(table_rows_host && d_tables_host && (plan || N == 0) && (grad_out || N == 0), "null buffer");
+// d_tables of the sorted reduction; the gradient operand is `grad_out` (node rows) or, with a row map, the token rows `gtok`
+static int bwd_sorted_impl(const char* fn, int num_tables, const int64_t* table_rows_host, int src, const float* grad_out, const void* gtok,
+                           const int32_t* rowmap, int64_t N, int64_t D, const void* plan, float* const* d_tables_host, void* workspace,
+                           size_t workspace_bytes, hipStream_t stream) {
   if (!workspace || workspace_bytes < gt_embed_sum_bwd_sorted_workspace_bytes(num_tables, N, D)) {
-    gt_set_error("gt_embed_sum_bwd_sorted: workspace too small");
+    gt_set_error("%s: workspace too small", fn);
     return GT_ERR_WORKSPACE;
   }
-  hipStream_t stream = (hipStream_t)stream_;
   const SortLayout L = sort_layout(num_tables, table_rows_host, N);
   // rows nobody indexes get zero: one memset per run of tables that lie back to back (the fused path's flat gradient buffer
   // holds them contiguously: one launch instead of one per table)
@@ -615,7 +667,7 @@ extern "C" int gt_embed_sum_bwd_sorted(int num_tables, const int64_t* table_rows
   }
   if (N == 0) return GT_OK;
   SegArgs a{};
-  a.T = num_tables; a.N = N; a.D = D; a.nchunks = (int)gt_cdiv(N, SEG_CH); a.g = grad_out;
+  a.T = num_tables; a.N = N; a.D = D; a.nchunks = (int)gt_cdiv(N, SEG_CH); a.g = grad_out; a.gtok = gtok; a.rowmap = rowmap;
   const char* pb = static_cast<const char*>(plan);
   a.bin_start = reinterpret_cast<const int32_t*>(pb + L.bin_off);
   a.order = reinterpret_cast<const int32_t*>(pb + L.order_off);
@@ -623,8 +675,85 @@ extern "C" int gt_embed_sum_bwd_sorted(int num_tables, const int64_t* table_rows
   for (int t = 0; t < num_tables; ++t) { a.row_off[t] = L.row_off[t]; a.rows[t] = table_rows_host[t]; a.dtable[t] = d_tables_host[t]; }
   a.head = static_cast<float*>(workspace);
   a.tail = a.head + (size_t)num_tables * a.nchunks * D;
-  hipLaunchKernelGGL(k_eseg_reduce, dim3(a.nchunks, num_tables), dim3(SEG_T), 0, stream, a);
-  hipLaunchKernelGGL(k_eseg_fixup, dim3(a.nchunks, num_tables), dim3(SEG_T), 0, stream, a);
+  const dim3 grid(a.nchunks, num_tables);
+  if (src == SEG_SRC_NODES) hipLaunchKernelGGL(k_eseg_reduce<SEG_SRC_NODES>, grid, dim3(SEG_T), 0, stream, a);
+  else if (src == SEG_SRC_TOK_F32) hipLaunchKernelGGL(k_eseg_reduce<SEG_SRC_TOK_F32>, grid, dim3(SEG_T), 0, stream, a);
+  else hipLaunchKernelGGL(k_eseg_reduce<SEG_SRC_TOK_BF16>, grid, dim3(SEG_T), 0, stream, a);
+  hipLaunchKernelGGL(k_eseg_fixup, grid, dim3(SEG_T), 0, stream, a);
+  return GT_OK;
+}
+
+extern "C" int gt_embed_sum_bwd_sorted(int num_tables, const int64_t* table_rows_host, const float* grad_out, int64_t N,
+                                       int64_t D, const void* plan, float* const* d_tables_host, void* workspace,
+                                       size_t workspace_bytes, gt_stream_t stream_) {
+  int rc = emb_check("gt_embed_sum_bwd_sorted", num_tables, N, D);
+  if (rc) return rc;
+  GT_CHECK_ARG(table_rows_host && d_tables_host && (plan || N == 0) && (grad_out || N == 0), "null buffer");
+  rc = bwd_sorted_impl("gt_embed_sum_bwd_sorted", num_tables, table_rows_host, SEG_SRC_NODES, grad_out, nullptr, nullptr, N, D, plan,
+                       d_tables_host, workspace, workspace_bytes, (hipStream_t)stream_);
+  if (rc) return rc;
+  GT_CHECK_LAUNCH();
+  return GT_OK;
+}
+
+// ---- embed -> token rows (the plain Transformer model's input: no [N][D] node matrix in between) ---------------------------------
+static int tok_check(const char* fn, int num_tables, int64_t N, int64_t D, int tok_dtype) {
+  int rc = emb_check(fn, num_tables, N, D);
+  if (rc) return rc;
+  if (tok_dtype != GT_F32 && tok_dtype != GT_BF16) { gt_set_error("%s: token dtype must be GT_F32 or GT_BF16", fn); return GT_ERR_UNSUPPORTED; }
+  if (tok_dtype == GT_BF16 && D % 8) { gt_set_error("%s: dim must be a multiple of 8 for bf16 tokens", fn); return GT_ERR_UNSUPPORTED; }
+  if (N >= (int64_t)1 << 31) { gt_set_error("%s: more than 2^31 nodes", fn); return GT_ERR_UNSUPPORTED; }
+  return GT_OK;
+}
+
+extern "C" int gt_embed_tokens_fwd(int num_tables, const int64_t* const* idx_ptrs_host, const int64_t* idx_strides_host,
+                                   const int64_t* clamp_max_host, const float* const* tables_host, const float* add, const int32_t* rows,
+                                   int64_t N, int64_t D, int tok_dtype, void* tokens, gt_stream_t stream_) {
+  int rc = tok_check("gt_embed_tokens_fwd", num_tables, N, D, tok_dtype);
+  if (rc) return rc;
+  GT_CHECK_ARG(idx_ptrs_host && idx_strides_host && clamp_max_host && tables_host, "null host array");
+  GT_CHECK_ARG(N == 0 || (rows && tokens), "null rows / tokens");
+  GT_CHECK_ARG(!(((uintptr_t)add | (uintptr_t)tokens) & 15), "the row operand and the token matrix are 16-byte aligned");
+  EmbArgs a{};
+  a.T = num_tables; a.N = N; a.D = D; a.add = add; a.add_before = add ? num_tables : -1;
+  for (int t = 0; t < num_tables; ++t) {
+    a.idx[t] = idx_ptrs_host[t]; a.stride[t] = idx_strides_host[t]; a.clamp[t] = clamp_max_host[t]; a.table[t] = tables_host[t];
+    GT_CHECK_ARG(a.idx[t] && a.table[t], "null table / index pointer");
+  }
+  if (N == 0) return GT_OK;
+  const dim3 grid(grid_for(N * (D / 4)));
+  if (tok_dtype == GT_F32) hipLaunchKernelGGL(k_embed_tokens_fwd<float>, grid, dim3(ET), 0, (hipStream_t)stream_, a, rows, (float*)tokens);
+  else hipLaunchKernelGGL(k_embed_tokens_fwd<gt_bf16>, grid, dim3(ET), 0, (hipStream_t)stream_, a, rows, (gt_bf16*)tokens);
+  GT_CHECK_LAUNCH();
+  return GT_OK;
+}
+
+extern "C" size_t gt_embed_tokens_bwd_workspace_bytes(int num_tables, int64_t N, int64_t D) {
+  return gt_embed_sum_bwd_sorted_workspace_bytes(num_tables, N, D);
+}
+
+extern "C" int gt_embed_tokens_bwd(int num_tables, const int64_t* table_rows_host, int tok_dtype, const void* d_tokens, const int32_t* rows,
+                                   int64_t N, int64_t D, const void* plan, float* const* d_tables_host, float* d_add, void* workspace,
+                                   size_t workspace_bytes, gt_stream_t stream_) {
+  int rc = tok_check("gt_embed_tokens_bwd", num_tables, N, D, tok_dtype);
+  if (rc) return rc;
+  GT_CHECK_ARG(table_rows_host && d_tables_host, "null host array");
+  GT_CHECK_ARG(N == 0 || (plan && d_tokens && rows), "null plan / d_tokens / rows");
+  GT_CHECK_ARG(!(((uintptr_t)d_add | (uintptr_t)d_tokens) & 15), "d_add and d_tokens are 16-byte aligned");
+  for (int t = 0; t < num_tables; ++t)
+    if (table_rows_host[t] < 1 || table_rows_host[t] > MAX_SORT_ROWS) {
+      gt_set_error("gt_embed_tokens_bwd: table %d has %lld rows (1..%d supported)", t, (long long)table_rows_host[t], MAX_SORT_ROWS);
+      return GT_ERR_UNSUPPORTED;
+    }
+  hipStream_t stream = (hipStream_t)stream_;
+  rc = bwd_sorted_impl("gt_embed_tokens_bwd", num_tables, table_rows_host, tok_dtype == GT_F32 ? SEG_SRC_TOK_F32 : SEG_SRC_TOK_BF16, nullptr,
+                       d_tokens, rows, N, D, plan, d_tables_host, workspace, workspace_bytes, stream);
+  if (rc) return rc;
+  if (d_add && N > 0) {
+    const dim3 grid(grid_for(N * (D / 4)));
+    if (tok_dtype == GT_F32) hipLaunchKernelGGL(k_embed_tokens_dadd<float>, grid, dim3(ET), 0, stream, (const float*)d_tokens, rows, N, D, d_add);
+    else hipLaunchKernelGGL(k_embed_tokens_dadd<gt_bf16>, grid, dim3(ET), 0, stream, (const gt_bf16*)d_tokens, rows, N, D, d_add);
+  }
   GT_CHECK_LAUNCH();
   return GT_OK;
 }

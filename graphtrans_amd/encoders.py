@@ -22,10 +22,15 @@ class ASTNodeEncoder(torch.nn.Module):
         self.attribute_encoder = torch.nn.Embedding(num_nodeattributes, emb_dim)
         self.depth_encoder = torch.nn.Embedding(self.max_depth + 1, emb_dim)
 
+    def embed_columns(self, x, depth):
+        """(index columns, tables, clamps) of the sum forward computes: the arguments of ops.embed_sum / ops.embed_tokens"""
+        return ([x[:, 0], x[:, 1], depth.reshape(-1)],
+                [self.type_encoder.weight, self.attribute_encoder.weight, self.depth_encoder.weight],
+                [None, None, self.max_depth])
+
     def forward(self, x, depth):
-        return ops.embed_sum([x[:, 0], x[:, 1], depth.reshape(-1)],
-                             [self.type_encoder.weight, self.attribute_encoder.weight, self.depth_encoder.weight],
-                             clamps=[None, None, self.max_depth])
+        columns, tables, clamps = self.embed_columns(x, depth)
+        return ops.embed_sum(columns, tables, clamps=clamps)
 
 
 class _SumEmbedding(torch.nn.Module):
@@ -39,17 +44,26 @@ class _SumEmbedding(torch.nn.Module):
         return embs
 
     @staticmethod
-    def _sum(embs, x):
+    def _columns(embs, x):
         cols = x.shape[1]
         if cols > 16:
             raise ValueError("at most 16 categorical columns")
-        return ops.embed_sum([x[:, i] for i in range(cols)], [embs[i].weight for i in range(cols)])
+        return [x[:, i] for i in range(cols)], [embs[i].weight for i in range(cols)], None
+
+    @staticmethod
+    def _sum(embs, x):
+        columns, tables, clamps = _SumEmbedding._columns(embs, x)
+        return ops.embed_sum(columns, tables, clamps)
 
 
 class AtomEncoder(_SumEmbedding):
     def __init__(self, emb_dim):
         super().__init__()
         self._build(ATOM_FEATURE_DIMS, emb_dim, "atom_embedding_list")
+
+    def embed_columns(self, x):
+        """(index columns, tables, clamps): the arguments of ops.embed_sum / ops.embed_tokens"""
+        return self._columns(self.atom_embedding_list, x)
 
     def forward(self, x):
         return self._sum(self.atom_embedding_list, x)
@@ -59,6 +73,9 @@ class BondEncoder(_SumEmbedding):
     def __init__(self, emb_dim):
         super().__init__()
         self._build(BOND_FEATURE_DIMS, emb_dim, "bond_embedding_list")
+
+    def embed_columns(self, edge_attr):
+        return self._columns(self.bond_embedding_list, edge_attr)
 
     def forward(self, edge_attr):
         return self._sum(self.bond_embedding_list, edge_attr)

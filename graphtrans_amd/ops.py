@@ -880,18 +880,122 @@ class _EmbedSum(torch.autograd.Function):
         return (None, *grads)
 
 
-def embed_sum(columns, tables, clamps=None):
-    """out[n] = sum_t tables[t][min(columns[t][n], clamps[t])].  `columns[t]` is an int64 device
-    tensor of shape (N,), possibly a strided view of an (N, C) matrix (no copy is made)."""
+def _embed_cols(columns, clamps, what):
     cols = []
     for t, c in enumerate(columns):
         if c.dtype != torch.int64 or c.dim() != 1:
-            raise TypeError("embed_sum: index columns must be 1-D int64")
+            raise TypeError(what + ": index columns must be 1-D int64")
         if not c.is_cuda:
             raise RuntimeError("index must be a GPU tensor: graphtrans_amd has no CPU fallback")
         clamp = -1 if clamps is None or clamps[t] is None else int(clamps[t])
         cols.append((c, 0, c.stride(0) if c.shape[0] > 1 else 1, clamp))
-    return _EmbedSum.apply(cols, *tables)
+    return cols
+
+
+def embed_sum(columns, tables, clamps=None):
+    """out[n] = sum_t tables[t][min(columns[t][n], clamps[t])].  `columns[t]` is an int64 device
+    tensor of shape (N,), possibly a strided view of an (N, C) matrix (no copy is made)."""
+    return _EmbedSum.apply(_embed_cols(columns, clamps, "embed_sum"), *tables)
+
+
+class _EmbedTokens(torch.autograd.Function):
+    """tokens[row of node n] = T(sum_t table_t[min(idx_t[n], clamp_t)] + perturb[n]), CLS rows = T(cls): gt_seq_token_rows (the row
+    map and the CLS rows) + gt_embed_tokens_fwd; the backward reads the token-row gradient through the map (gt_embed_tokens_bwd) and
+    sums its CLS rows (gt_colsum_rows_f32)."""
+
+    @staticmethod
+    def forward(ctx, cols, gs, lay, out_dtype, cls, perturb, *tables):
+        T = len(tables)
+        tables = [_dev(t, "table") for t in tables]
+        D = tables[0].shape[1]
+        N = gs.N
+        dev = tables[0].device
+        I64, P = C.c_int64 * T, C.c_void_p * T
+        idx = P(*[c[0].data_ptr() + 8 * c[1] for c in cols])
+        strides = I64(*[c[2] for c in cols])
+        clamp = I64(*[c[3] for c in cols])
+        tabs = P(*[t.data_ptr() for t in tables])
+        code = GT_F32 if out_dtype == torch.float32 else GT_BF16
+        tokens = (torch.empty if getattr(lay, "exact", True) else torch.zeros)((lay.rows, D), dtype=out_dtype, device=dev)
+        rowmap = torch.empty(max(N, 1), dtype=torch.int32, device=dev)
+        cls32 = None if cls is None else _dev(cls.detach().reshape(-1).float(), "cls")
+        add = None if perturb is None else _dev(perturb.detach().float(), "perturb")
+        _lib.launch("gt_seq_token_rows", code, _ptr(cls32), _ptr(gs.graph_ptr), _ptr(gs.node_graph), _ptr(lay.desc), lay.B, lay.row_stride,
+                    1 if lay.with_cls else 0, N, D, _ptr(tokens), _ptr(rowmap), _stream())
+        _lib.launch("gt_embed_tokens_fwd", T, idx, strides, clamp, tabs, _ptr(add), _ptr(rowmap), N, D, code, _ptr(tokens), _stream())
+        rows = [t.shape[0] for t in tables]
+        ctx.cols, ctx.meta = cols, (T, N, D, rows, dev, code, out_dtype)
+        ctx.lay, ctx.rowmap, ctx.plan = lay, rowmap, None
+        ctx.cls_meta = None if cls is None else (cls.shape, cls.dtype)
+        ctx.perturb_dtype = None if perturb is None else perturb.dtype
+        if any(t.requires_grad for t in tables):
+            # the backward sums each table row's gradient rows in node order: sort the node ids by row now (as _EmbedSum does)
+            L = _lib.lib()
+            rows_c = I64(*rows)
+            plan = torch.empty(L.gt_embed_sort_plan_bytes(T, rows_c, N), dtype=torch.uint8, device=dev)
+            wsb = L.gt_embed_sort_workspace_bytes(T, rows_c, N)
+            ws = torch.empty(wsb, dtype=torch.uint8, device=dev)
+            _lib.launch("gt_embed_sort", T, idx, strides, clamp, rows_c, N, _ptr(plan), plan.numel(), _ptr(ws), wsb, _stream())
+            ctx.plan = plan
+        return tokens
+
+    @staticmethod
+    def backward(ctx, g):
+        T, N, D, rows, dev, code, out_dtype = ctx.meta
+        lay = ctx.lay
+        g = _dev(g.to(out_dtype), "grad")
+        I64, P = C.c_int64 * T, C.c_void_p * T
+        rows_c = I64(*rows)
+        dcls = dadd = None
+        if ctx.cls_meta is not None and ctx.needs_input_grad[4]:
+            dcls = torch.empty(D, dtype=torch.float32, device=dev)
+            _lib.launch("gt_colsum_rows_f32", code, _ptr(g), _ptr(lay.last_rows), lay.B, D, _ptr(dcls), _stream())
+            dcls = dcls.reshape(ctx.cls_meta[0]).to(ctx.cls_meta[1])
+        if ctx.perturb_dtype is not None and ctx.needs_input_grad[5]:
+            dadd = torch.empty((N, D), dtype=torch.float32, device=dev)
+        grads = [torch.empty((r, D), dtype=torch.float32, device=dev) if (ctx.plan is not None and ctx.needs_input_grad[6 + t]) else None
+                 for t, r in enumerate(rows)]
+        if dadd is not None or any(x is not None for x in grads):
+            if ctx.plan is None:   # only d perturb is asked for: no table is reduced, the plan is never read
+                ctx.plan = torch.empty(16, dtype=torch.uint8, device=dev)
+            dt = P(*[(x.data_ptr() if x is not None else None) for x in grads])
+            ws_bytes = _lib.lib().gt_embed_tokens_bwd_workspace_bytes(T, N, D)
+            ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
+            _lib.launch("gt_embed_tokens_bwd", T, rows_c, code, _ptr(g), _ptr(ctx.rowmap), N, D, _ptr(ctx.plan), dt, _ptr(dadd), _ptr(ws),
+                        ws_bytes, _stream())
+        if dadd is not None:
+            dadd = dadd.to(ctx.perturb_dtype)
+        return (None, None, None, None, dcls, dadd, *grads)
+
+
+def embed_tokens_supported(columns, tables, gs, lay, out_dtype=torch.float32):
+    """What ops.embed_tokens takes: a packed layout (no pad rows), 1 .. 16 fp32 GPU tables of one width and at most EMBED_SORT_MAX_ROWS
+    rows each, a width that is a multiple of 4 (fp32 tokens) / 8 (bf16 tokens), 1-D int64 GPU index columns of gs.N entries."""
+    if getattr(lay, "kind", None) != "packed" or lay.row_stride != 1 or out_dtype not in (torch.float32, torch.bfloat16):
+        return False
+    if not (1 <= len(tables) <= 16 and len(columns) == len(tables)):
+        return False
+    D = tables[0].shape[-1]
+    if D % (8 if out_dtype == torch.bfloat16 else 4):
+        return False
+    for t in tables:
+        if not (t.is_cuda and t.dtype == torch.float32 and t.dim() == 2 and t.shape[1] == D and 1 <= t.shape[0] <= EMBED_SORT_MAX_ROWS):
+            return False
+    return all(c.is_cuda and c.dtype == torch.int64 and c.dim() == 1 and c.shape[0] == gs.N for c in columns)
+
+
+def embed_tokens(columns, tables, clamps, gs, lay, cls=None, perturb=None, out_dtype=torch.float32):
+    """The token matrix (lay.rows, D) of a model whose token rows ARE the input encoder's rows (models/transformer.py):
+    tokens[row of node n] = out_dtype(sum_t tables[t][min(columns[t][n], clamps[t])] + perturb[n]) and the CLS rows = out_dtype(cls),
+    what embed_sum -> + perturb -> seq_gather -> .to(out_dtype) gives, bit for bit, without the (N, D) node matrix.  One autograd
+    node: gradients go to the tables, to `cls` and to `perturb` (fp32 (N, D); the dropped nodes of a truncated graph get zero rows)."""
+    if not embed_tokens_supported(columns, tables, gs, lay, out_dtype):
+        raise ValueError("embed_tokens: unsupported arguments (ops.embed_tokens_supported)")
+    if (cls is not None) != bool(lay.with_cls):
+        raise ValueError("embed_tokens: cls must be given exactly when the layout has CLS rows")
+    if perturb is not None and (not perturb.is_cuda or tuple(perturb.shape) != (gs.N, tables[0].shape[1])):
+        raise ValueError("embed_tokens: perturb must be a GPU tensor with one row per node")
+    return _EmbedTokens.apply(_embed_cols(columns, clamps, "embed_tokens"), gs, lay, out_dtype, cls, perturb, *tables)
 
 
 # ------------------------------------------------------------------------------------------------

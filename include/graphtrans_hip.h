@@ -305,6 +305,27 @@ size_t gt_embed_sum_bwd_sorted_workspace_bytes(int num_tables, int64_t num_nodes
 int gt_embed_sum_bwd_sorted(int num_tables, const int64_t* table_rows_host, const float* grad_out, int64_t num_nodes,
                             int64_t dim, const void* plan, float* const* d_tables_host, void* workspace,
                             size_t workspace_bytes, gt_stream_t stream);
+/* The input encoder written straight into the token matrix (the plain Transformer model, models/transformer.py:87-101: node
+ * encoder -> + perturb -> pad_batch, with no [num_nodes][dim] matrix in between).  For every node n with rows[n] >= 0:
+ *   tokens[rows[n]] = T(sum_t table_t[min(idx_t[n], clamp_t)] + add[n])
+ * the sum in fp32, in table order, `add` last (gt_embed_sum_fwd_add with add_before == num_tables, bit for bit), then ONE
+ * round-to-nearest-even conversion to tok_dtype (GT_F32 | GT_BF16).  add: fp32 [num_nodes][dim] or NULL (the FLAG perturbation);
+ * rows: int32 [num_nodes], the map gt_seq_token_rows writes (-1: a leading node its truncated graph drops; such a node is neither
+ * read nor written), so only layouts WITHOUT pad rows; the CLS rows stay with gt_seq_token_rows.  Nothing else of `tokens` is
+ * written.  dim % 4 == 0 (fp32 tokens) / dim % 8 == 0 (bf16 tokens), 1 .. 16 tables: anything else is GT_ERR_UNSUPPORTED before
+ * any launch. */
+int gt_embed_tokens_fwd(int num_tables, const int64_t* const* idx_ptrs_host, const int64_t* idx_strides_host,
+                        const int64_t* clamp_max_host, const float* const* tables_host, const float* add, const int32_t* rows,
+                        int64_t num_nodes, int64_t dim, int tok_dtype, void* tokens, gt_stream_t stream);
+/* Its backward: gt_embed_sum_bwd_sorted (same plan from gt_embed_sort, same summation order: node order within each table row, no
+ * atomics; tables of up to 16384 rows) whose gradient operand is read through the row map: the value of node n is
+ * float(d_tokens[rows[n]]), 0.f where rows[n] < 0.  Table rows no node hits get exactly 0; d_tables_host[t] may be NULL.
+ * d_add: fp32 [num_nodes][dim] or NULL, gets the same per-node values (zero rows for the dropped nodes).  The gradient of the
+ * CLS row is gt_colsum_rows_f32 over the CLS rows. */
+size_t gt_embed_tokens_bwd_workspace_bytes(int num_tables, int64_t num_nodes, int64_t dim);
+int gt_embed_tokens_bwd(int num_tables, const int64_t* table_rows_host, int tok_dtype, const void* d_tokens, const int32_t* rows,
+                        int64_t num_nodes, int64_t dim, const void* plan, float* const* d_tables_host, float* d_add,
+                        void* workspace, size_t workspace_bytes, gt_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------------
  * Per-graph segment ops on the sorted `batch` vector (virtual node + pooling).
