@@ -8,6 +8,9 @@
 // arena book-keeping: 2.3 ms of interpreter time per Code2 step against ~1 ms of launches).  Here the same calls are issued
 // from C in the same order on the same three streams; the caller supplies one arena per direction.
 // Pure host code + nothing allocated or synchronised: every buffer is the caller's.
+// Three modes share the code: the token path above, the read-out mode (gt_model::readout: message passing -> pooling -> heads, the GNN /
+// PNA baselines) and the encoder-only mode (gt_model::enc_only: no message passing, the input encoder's rows are the token rows, the
+// Transformer baseline of models/transformer.py:87-101) -- forward_enc_only_tokens + forward_encoder, Bwd::encoder / input_encoder.
 //
 // gt_model_prepare DECIDES: every question about which kernel or which stream a step takes is asked there, once, with the weight
 // images bound, and the answers are stored in the context (Decisions); the arenas are sized beside them.  gt_model_forward and
@@ -122,6 +125,21 @@ int model_check(const char* fn, const gt_model* m) {
   if (!m) { gt_set_error("%s: null model", fn); return GT_ERR_INVALID_ARG; }
   // (n_enc == 0 is legal in the reference's GNNTransformer -- it pools the token rows themselves -- but not built here: the callers route it
   // to the module path.  The read-out mode -- the GNN baseline, gt_model::readout -- has no encoder at all: there n_enc == 0 is required)
+  if (m->enc_only) {   // the encoder-only mode (the Transformer baseline): checked here on its own, every other model exactly as below
+    if (m->L != 0 || m->n_enc < 1 || m->n_enc > MAXL || !m->with_cls || m->readout || m->jk_cat || m->has_vn || m->pe || m->head_kind) {
+      gt_set_error("%s: the encoder-only mode takes L == 0, 1..%d encoder layers, a CLS row, no read-out, JK = last, no virtual node, no "
+                   "positional encoding and the linear heads", fn, MAXL);
+      return GT_ERR_INVALID_ARG;
+    }
+    if (!m->enc || !m->cls || !m->head_w || !m->head_b) { gt_set_error("%s: null descriptor array", fn); return GT_ERR_INVALID_ARG; }
+    if (m->d <= 0 || m->d % 8 || m->D != m->d) { gt_set_error("%s: bad widths (the encoder-only mode has D == d)", fn); return GT_ERR_INVALID_ARG; }
+    const bool lin = m->embed_kind == 1;
+    if (lin ? (!m->ne_w || !m->ne_b || m->ne_K < 1) : (m->n_tables < 1 || m->n_tables > MAXT || !m->embed_sorted)) {
+      gt_set_error("%s: the encoder-only mode takes a Linear input encoder with its bias, or 1..%d tables the sorted backward covers", fn, MAXT);
+      return GT_ERR_INVALID_ARG;
+    }
+    return GT_OK;
+  }
   const bool ro = m->readout != 0;
   if (m->L < 1 || m->L > MAXL || (ro ? m->n_enc != 0 : (m->n_enc < 1 || m->n_enc > MAXL)) || m->n_tables < 0 || m->n_tables > MAXT) {
     gt_set_error("%s: layer / table counts out of range", fn);
@@ -373,6 +391,15 @@ int prepare_decisions(const gt_model* m, const gt_model_batch* b, Ctx* c) {
   const int L = m->L;
   const bool frozen = b->gnn_frozen != 0, gcn = m->conv == GT_CONV_GCN;
   Decisions& k = c->k;
+  if (m->enc_only) {
+    // the encoder-only mode asks nothing of a GEMM: the table encoders always write the token rows through the row map
+    // (gt_embed_tokens_fwd), the Linear encoder always goes through [N][d] rows and the gather -- its weight, re-pitched into the arena
+    // at every forward (K % 4 != 0: the 37 TU features), can never have a bound image, which the row-map GEMM needs
+    k.fuse_rows = m->embed_kind != 1 ? 1 : 0;
+    k.esort = (b->will_bwd && m->embed_kind != 1) ? 1 : 0;   // the sort plan IS the table backward's input here (model_check: embed_sorted)
+    k.ov = (m->st_dw && N * D >= m->dw_overlap_min_elems) ? 1 : 0;
+    return GT_OK;
+  }
   BindGuard guard;   // (thread-local bind tables: bound for the questions)
   GT_TRY(bind_images(m, c));
   // the prep stream pays for its stream switches and events (~0.4 ms of host time per step) only when the structure kernels are long:
@@ -424,7 +451,8 @@ void prepare_forward_arena(const gt_model* m, const gt_model_batch* b, Ctx* c) {
   const int L = m->L, nenc = m->n_enc, nvn = m->has_vn ? L - 1 : 0;
   const size_t tsz = c->tsz, ND4 = (size_t)N * D * 4;
   Bump a;
-  for (int l = 0; l <= L; ++l) c->o_h[l] = a.take(ND4);
+  const bool eo = m->enc_only != 0;   // no node-row matrices: the token rows are the input encoder's output
+  for (int l = 0; l <= L; ++l) c->o_h[l] = a.take(eo ? 0 : ND4);
   if (m->has_vn) {
     c->o_x0 = a.take(m->vn0_in_embed ? 0 : ND4);
     for (int l = 0; l < L; ++l) c->o_vn[l] = a.take((size_t)B * D * 4);
@@ -433,7 +461,8 @@ void prepare_forward_arena(const gt_model* m, const gt_model_batch* b, Ctx* c) {
   for (int l = 0; l < L; ++l) c->o_conv_saved[l] = a.take(conv_saved_bytes(m, c, l));
   c->o_cat = a.take((m->jk_cat && !c->k.cat2) ? (size_t)N * Kc * 4 : 0);
   const bool ro = m->readout != 0;   // no gnn2transformer, no token rows, no encoder: their slots are empty
-  c->o_hn = a.take(ro ? 0 : (size_t)N * d * (m->pe ? 4 : tsz));   // (fp32 under a positional encoding: its add comes before the one rounding)
+  // (fp32 under a positional encoding: its add comes before the one rounding; encoder-only mode: the Linear encoder's rows, no table's)
+  c->o_hn = a.take((ro || (eo && m->embed_kind != 1)) ? 0 : (size_t)N * d * (m->pe ? 4 : tsz));
   c->o_rowmap = a.take(ro ? 0 : (size_t)N * 4);
   c->o_pos = a.take(m->pe ? (size_t)N * 4 : 0);
   c->o_tok = a.take(ro ? 0 : (size_t)rows * d * tsz);
@@ -504,7 +533,8 @@ void prepare_backward_arena(const gt_model* m, const gt_model_batch* b, Ctx* c) 
   const int64_t N = b->N, B = b->B, D = m->D, d = m->d, rows = c->rows, Kc = c->Kc;
   const int L = m->L, nenc = m->n_enc;
   const size_t tsz = c->tsz, ND4 = (size_t)N * D * 4;
-  const bool frozen = b->gnn_frozen != 0;
+  const bool eo = m->enc_only != 0;
+  const bool frozen = b->gnn_frozen != 0 || eo;   // (encoder-only mode: no message passing either, its slots are as empty as a frozen stack's)
   const bool ro = m->readout != 0;   // heads on the pooled rows [B][D]; the pooling's backward writes d h_list[-1] into q_d_rep
   const int64_t hk = ro ? D : d;     // the heads' input width
   Bump q;
@@ -513,8 +543,8 @@ void prepare_backward_arena(const gt_model* m, const gt_model_batch* b, Ctx* c) 
   c->q_dyp = q.take(ro ? 0 : (size_t)B * d * tsz);
   c->q_dtok[0] = q.take(ro ? 0 : (size_t)rows * d * tsz);
   c->q_dtok[1] = q.take(ro ? 0 : (size_t)rows * d * tsz);
-  c->q_d_hn = q.take(ro ? 0 : (size_t)N * d * tsz);
-  c->q_d_cls = q.take(ro ? 0 : (size_t)B * d * tsz);
+  c->q_d_hn = q.take((ro || (eo && m->embed_kind != 1)) ? 0 : (size_t)N * d * tsz);
+  c->q_d_cls = q.take((ro || eo) ? 0 : (size_t)B * d * tsz);
   // (frozen message-passing stack: the node-row and virtual-node gradients are never made, their slots are empty)
   c->q_d_rep = q.take(frozen ? 0 : (size_t)N * Kc * 4);
   c->q_dA = q.take(frozen ? 0 : ND4); c->q_dB = q.take(frozen ? 0 : ND4); c->q_dC = q.take(frozen ? 0 : ND4);
@@ -530,7 +560,7 @@ void prepare_backward_arena(const gt_model* m, const gt_model_batch* b, Ctx* c) 
   size_t emb_ws;
   if (m->embed_kind == 1) {
     emb_ws = gt_linear_bwd_workspace_bytes(c->compute, N, D, Kp);
-    c->q_ne_dw = q.take((Kp != m->ne_K && !frozen) ? (size_t)D * Kp * 4 : 0);
+    c->q_ne_dw = q.take((Kp != m->ne_K && (!frozen || eo)) ? (size_t)D * Kp * 4 : 0);
   } else if (c->k.esort) {
     emb_ws = gt_embed_sum_bwd_sorted_workspace_bytes(c->T, N, D);
   } else {
@@ -646,6 +676,14 @@ extern "C" size_t gt_model_ctx_bytes(void) { return sizeof(Ctx); }
 extern "C" int gt_model_grad_ranges(const gt_model* m, int64_t* lo3, int64_t* hi3) {
   GT_TRY(model_check("gt_model_grad_ranges", m));
   GT_CHECK_ARG(lo3 && hi3, "null output");
+  if (m->enc_only) {   // no message passing: the middle range is empty, the input encoder's block ends where the CLS embedding's begins
+    const int64_t t = m->off_cls;
+    GT_CHECK_ARG(t >= 0 && t <= m->grad_total, "the encoder-only mode's gradient layout: input encoder, cls_embedding, ...");
+    lo3[0] = t; hi3[0] = m->grad_total;
+    lo3[1] = t; hi3[1] = t;
+    lo3[2] = 0; hi3[2] = t;
+    return GT_OK;
+  }
   const int64_t gnn_lo = m->has_vn ? m->off_vn_emb : m->off_conv[0];
   // (read-out mode: no gnn2transformer, the heads follow message passing; their hidden layers lead the head block)
   const int64_t tail = m->readout ? (m->head_kind ? m->off_hid_w : m->off_head_w) : m->off_g2t_w;
@@ -660,7 +698,12 @@ extern "C" int gt_model_prepare(const gt_model* m, const gt_model_batch* b, void
   GT_TRY(model_check("gt_model_prepare", m));
   GT_CHECK_ARG(b && ctx_ && out, "null argument");
   GT_CHECK_ARG(b->N > 0 && b->B > 0 && b->E >= 0, "empty batch");
-  GT_CHECK_ARG(b->x && ((b->edge_index && b->batch) || b->graph_ptr), "null batch arrays");
+  // (encoder-only mode: the batch's edges are not this model's input, `batch` alone builds the structure it reads)
+  GT_CHECK_ARG(b->x && (((b->edge_index || m->enc_only) && b->batch) || b->graph_ptr), "null batch arrays");
+  if (m->enc_only) {   // refused before anything is launched: these combinations stay on the module path
+    GT_CHECK_ARG(!b->gnn_frozen, "the encoder-only mode has no message-passing stack to freeze");
+    GT_CHECK_ARG(!(b->perturb && m->embed_kind == 1), "the encoder-only mode takes a perturbation with the table encoders only");
+  }
   // the perturbation of forward(batched_data, perturb) and its gradient (gt_model_batch::perturb / d_perturb)
   GT_CHECK_ARG(!(b->perturb && b->gnn_frozen), "perturb with gnn_frozen: a frozen message-passing stack hands out no d perturb");
   GT_CHECK_ARG(!b->d_perturb || (b->perturb && b->will_bwd), "d_perturb without perturb (or without will_bwd)");
@@ -673,6 +716,7 @@ extern "C" int gt_model_prepare(const gt_model* m, const gt_model_batch* b, void
   c->tdt = b->tdt;
   c->tsz = gt_elt_bytes(b->tdt);
   c->build_graph = b->graph_ptr == nullptr;
+  if (m->enc_only) c->in.E = 0;   // gt_graph_prep at E = 0: graph_ptr / node_graph (all this mode reads), no edge is touched or sorted
   if (m->readout) {   // no token layout (rows = num_work = 0, no staging-ring slot), no encoder weight images
     GT_CHECK_ARG(!b->gnn_frozen, "the read-out mode has no frozen message-passing stack (models/gnn.py has no freeze_gnn)");
     GT_CHECK_ARG(m->head_kind != 2 || b->B <= 4096, "the per-position heads take at most 4096 graphs per batch");
@@ -694,6 +738,110 @@ extern "C" int gt_model_prepare(const gt_model* m, const gt_model_batch* b, void
 }
 
 // =================================================================================================================================
+namespace {
+
+// the index columns, clamps and tables of a table input encoder (embed_kind 0 / 2) for the embedding kernels
+int embed_columns(const gt_model* m, Ctx* c, const float** tabs) {
+  const gt_model_batch& b = c->in;
+  const int T = c->T;
+  const int64_t* x = (const int64_t*)b.x;
+  if (m->embed_kind == 2) {   // ASTNodeEncoder: type, attribute, clamped depth
+    GT_CHECK_ARG(T == 3 && b.node_depth, "ASTNodeEncoder has three tables and needs node_depth");
+    c->e_idx[0] = x; c->e_str[0] = b.x_stride0;
+    c->e_idx[1] = x + b.x_stride1; c->e_str[1] = b.x_stride0;
+    c->e_idx[2] = b.node_depth; c->e_str[2] = b.depth_stride;
+  } else {
+    for (int t = 0; t < T; ++t) { c->e_idx[t] = x + (int64_t)t * b.x_stride1; c->e_str[t] = b.x_stride0; }
+  }
+  for (int t = 0; t < T; ++t) { c->e_clamp[t] = m->table_clamp[t]; tabs[t] = m->tables[t]; }
+  return GT_OK;
+}
+
+// ---- behind the token rows (c->o_tok; with Decisions::fuse_nin c->o_xin holds norm_input's output already): norm_input, the encoder
+// layers with the last one pooled, the final norm on the pooled rows, the heads, and the closing joins of the side streams.  Shared by
+// the token path and the encoder-only mode   (modules/transformer_encoder.py:42-61, models/gnn_transformer.py:113-126)
+int forward_encoder(const gt_model* m, Ctx* c, float* logits, gt_stream_t st) {
+  const gt_model_batch& b = c->in;
+  const Decisions& k = c->k;
+  const int64_t B = b.B, d = m->d, rows = c->rows;
+  const int nenc = m->n_enc, tdt = c->tdt, compute = c->compute;
+  auto P = [&](size_t off) -> void* { return c->base + off; };
+  const void* cur = P(c->o_tok);
+  if (k.fuse_nin) {
+    cur = P(c->o_xin);
+  } else if (m->nin_w) {
+    GT_TRY(gt_layernorm_fwd(tdt, cur, nullptr, m->nin_w, m->nin_b, m->nin_eps, 0.f, 0, rows, d, P(c->o_xin), (float*)P(c->o_st0),
+                            (float*)P(c->o_st0) + rows, st));
+    cur = P(c->o_xin);
+  }
+  for (int i = 0; i < nenc; ++i) {
+    c->enc_in[i] = cur;
+    if (i == nenc - 1) {   // only the pooled row of every sequence is read behind the last layer: y = [B][d]
+      GT_TRY(gt_encoder_layer_pooled_fwd(&c->enc[i], cur, c->last_rows, P(c->o_xe[i]), P(c->o_enc_saved[i]), st));
+    } else {
+      GT_TRY(gt_encoder_layer_fwd(&c->enc[i], cur, P(c->o_xe[i]), P(c->o_enc_saved[i]), st));
+    }
+    cur = P(c->o_xe[i]);
+  }
+  c->pre_out = cur;   // [B][d]: the pooled rows
+  if (m->nout_w) {
+    // transformer.norm (transformer_encoder.py:28-32) is row-wise: on the pooled rows (fp32 copies), forward and backward
+    GT_TRY(gt_rows_gather(tdt, cur, nullptr, B, d, (float*)P(c->o_hgin), st));
+    GT_TRY(gt_layernorm_fwd(GT_F32, P(c->o_hgin), nullptr, m->nout_w, m->nout_b, m->nout_eps, 0.f, 0, B, d, P(c->o_hg), (float*)P(c->o_sto),
+                            (float*)P(c->o_sto) + B, st));
+  } else {
+    GT_TRY(gt_rows_gather(tdt, cur, nullptr, B, d, (float*)P(c->o_hg), st));
+  }
+  // ---- prediction heads as one GEMM over the stacked weights   (gnn_transformer.py:120-126)
+  GT_TRY(gt_linear_fwd_ld(GT_F32, GT_F32, compute, P(c->o_hg), m->head_w, m->head_b, logits, B, m->Nh, d, m->ldy, 0, 0.f, 0, st));
+  // the side streams wrote into this arena: join them before anything can hand it back to the allocator
+  if (k.esort && m->st_dw) GT_TRY(gt_stream_wait_event(st, m->ev_sort[1]));
+  else if (k.want_wt && m->st_dw) GT_TRY(gt_stream_wait_event(st, m->ev_wt[1]));
+  return GT_OK;
+}
+
+// ---- the encoder-only mode's token rows (models/transformer.py:87-101: node encoder -> + perturb -> pad + CLS): the table encoders write
+// them straight from the tables through the row map, the Linear encoder goes through [N][d] rows of the token type and the gather
+int forward_enc_only_tokens(const gt_model* m, Ctx* c, gt_stream_t st) {
+  const gt_model_batch& b = c->in;
+  const Graph& g = c->g;
+  const int64_t N = b.N, B = b.B, d = m->d;
+  const int tdt = c->tdt;
+  auto P = [&](size_t off) -> void* { return c->base + off; };
+  if (m->embed_kind == 1) {   // nn.Linear(F, d) (dataset/tud.py:65) in gnn2transformer's place: x W^T + b, rounded once to the token type
+    const int64_t K = m->ne_K, Kp = (int64_t)c4((size_t)K);
+    const float *nx = (const float*)b.x, *nw = m->ne_w;
+    if (Kp != K) {
+      GT_TRY(gt_repitch(P(c->o_ne_x), Kp, b.x, K, N, 4, st));
+      GT_TRY(gt_repitch(P(c->o_ne_w), Kp, m->ne_w, K, d, 4, st));
+      nx = (const float*)P(c->o_ne_x); nw = (const float*)P(c->o_ne_w);
+    }
+    c->ne_x = nx; c->ne_w = nw;
+    GT_TRY(gt_linear_fwd(GT_F32, tdt, c->compute, nx, nw, m->ne_b, P(c->o_hn), N, d, Kp, 0, 0.f, 0, st));
+    return gt_seq_gather_cls32(tdt, P(c->o_hn), m->cls, g.graph_ptr, c->seq_desc, B, 1, c->max_npos, 1, d, P(c->o_tok), st);
+  }
+  const int T = c->T;
+  const float* tabs[MAXT + 1];
+  GT_TRY(embed_columns(m, c, tabs));
+  int32_t* rmap = (int32_t*)P(c->o_rowmap);
+  GT_TRY(gt_seq_token_rows(tdt, m->cls, g.graph_ptr, g.node_graph, c->seq_desc, B, 1, 1, N, d, P(c->o_tok), rmap, st));
+  GT_TRY(gt_embed_tokens_fwd(T, c->e_idx, c->e_str, c->e_clamp, tabs, b.perturb, rmap, N, d, tdt, P(c->o_tok), st));
+  if (c->k.esort) {   // node ids per table row for the backward: beside the encoder on the overlap stream, only the index columns are read
+    gt_stream_t sst = st;
+    if (m->st_dw) {
+      sst = m->st_dw;
+      GT_TRY(gt_event_record(m->ev_sort[0], st));
+      GT_TRY(gt_stream_wait_event(sst, m->ev_sort[0]));
+    }
+    GT_TRY(gt_embed_sort(T, c->e_idx, c->e_str, c->e_clamp, c->e_rows, N, P(c->o_eplan), c->eplan_bytes, P(c->o_esort_ws), c->esort_ws_bytes, sst));
+    if (m->st_dw) GT_TRY(gt_event_record(m->ev_sort[1], sst));
+  }
+  return GT_OK;
+}
+
+}  // namespace
+
+// =================================================================================================================================
 extern "C" int gt_model_forward(const gt_model* m, void* ctx_, void* arena, float* logits, gt_stream_t st) {
   GT_TRY(model_check("gt_model_forward", m));
   Ctx* c = (Ctx*)ctx_;
@@ -702,7 +850,7 @@ extern "C" int gt_model_forward(const gt_model* m, void* ctx_, void* arena, floa
   const gt_model_batch& b = c->in;
   const Decisions& k = c->k;
   const int64_t N = b.N, B = b.B, D = m->D, d = m->d, rows = c->rows;
-  const int L = m->L, nenc = m->n_enc, tdt = c->tdt, compute = c->compute, cls = m->with_cls ? 1 : 0;
+  const int L = m->L, tdt = c->tdt, compute = c->compute, cls = m->with_cls ? 1 : 0;
   c->base = (char*)arena;
   c->forwarded = 1;
   auto P = [&](size_t off) -> void* { return c->base + off; };
@@ -711,6 +859,11 @@ extern "C" int gt_model_forward(const gt_model* m, void* ctx_, void* arena, floa
   void* ev_w1 = nullptr;
   GT_TRY(forward_prologue(m, c, st, &ev_w1));
   const Graph& g = c->g;
+  if (m->enc_only) {   // no message passing, no gnn2transformer: the input encoder's rows are the token rows
+    if (ev_w1) GT_TRY(gt_stream_wait_event(st, ev_w1));
+    GT_TRY(forward_enc_only_tokens(m, c, st));
+    return forward_encoder(m, c, logits, st);
+  }
 
   gt_stream_t side = m->has_vn ? m->st_vn : nullptr;
   // ---- transposed weights for the backward's exact-fp32 dX GEMMs, written beside the forward
@@ -743,17 +896,8 @@ extern "C" int gt_model_forward(const gt_model* m, void* ctx_, void* arena, floa
     if (b.perturb)   // encoded + perturb (gnn_module.py:158), in place behind the GEMM
       GT_TRY(gt_add3((const float*)P(c->o_h[0]), b.perturb, nullptr, N * D, (float*)P(c->o_h[0]), st));
   } else {
-    const int64_t* x = (const int64_t*)b.x;
-    if (m->embed_kind == 2) {   // ASTNodeEncoder: type, attribute, clamped depth
-      GT_CHECK_ARG(T == 3 && b.node_depth, "ASTNodeEncoder has three tables and needs node_depth");
-      c->e_idx[0] = x; c->e_str[0] = b.x_stride0;
-      c->e_idx[1] = x + b.x_stride1; c->e_str[1] = b.x_stride0;
-      c->e_idx[2] = b.node_depth; c->e_str[2] = b.depth_stride;
-    } else {
-      for (int t = 0; t < T; ++t) { c->e_idx[t] = x + (int64_t)t * b.x_stride1; c->e_str[t] = b.x_stride0; }
-    }
     const float* tabs[MAXT + 1];
-    for (int t = 0; t < T; ++t) { c->e_clamp[t] = m->table_clamp[t]; tabs[t] = m->tables[t]; }
+    GT_TRY(embed_columns(m, c, tabs));
     int Tn = T;
     if (m->vn0_in_embed) {   // + virtualnode_embedding.weight[0] for every node (gnn_module.py:195,199): one more table, stride-0 index
       c->e_idx[T] = m->zero_i64; c->e_str[T] = 0; c->e_clamp[T] = -1; tabs[T] = m->vn_emb;
@@ -867,38 +1011,7 @@ extern "C" int gt_model_forward(const gt_model* m, void* ctx_, void* arena, floa
     else
       GT_TRY(gt_seq_gather_cls32(tdt, P(c->o_hn), m->cls, g.graph_ptr, c->seq_desc, B, 1, c->max_npos, cls, d, P(c->o_tok), st));
   }
-  const void* cur = P(c->o_tok);
-  if (k.fuse_nin) {
-    cur = P(c->o_xin);
-  } else if (m->nin_w) {
-    GT_TRY(gt_layernorm_fwd(tdt, cur, nullptr, m->nin_w, m->nin_b, m->nin_eps, 0.f, 0, rows, d, P(c->o_xin), (float*)P(c->o_st0),
-                            (float*)P(c->o_st0) + rows, st));
-    cur = P(c->o_xin);
-  }
-  for (int i = 0; i < nenc; ++i) {
-    c->enc_in[i] = cur;
-    if (i == nenc - 1) {   // only the pooled row of every sequence is read behind the last layer: y = [B][d]
-      GT_TRY(gt_encoder_layer_pooled_fwd(&c->enc[i], cur, c->last_rows, P(c->o_xe[i]), P(c->o_enc_saved[i]), st));
-    } else {
-      GT_TRY(gt_encoder_layer_fwd(&c->enc[i], cur, P(c->o_xe[i]), P(c->o_enc_saved[i]), st));
-    }
-    cur = P(c->o_xe[i]);
-  }
-  c->pre_out = cur;   // [B][d]: the pooled rows
-  if (m->nout_w) {
-    // transformer.norm (transformer_encoder.py:28-32) is row-wise: on the pooled rows (fp32 copies), forward and backward
-    GT_TRY(gt_rows_gather(tdt, cur, nullptr, B, d, (float*)P(c->o_hgin), st));
-    GT_TRY(gt_layernorm_fwd(GT_F32, P(c->o_hgin), nullptr, m->nout_w, m->nout_b, m->nout_eps, 0.f, 0, B, d, P(c->o_hg), (float*)P(c->o_sto),
-                            (float*)P(c->o_sto) + B, st));
-  } else {
-    GT_TRY(gt_rows_gather(tdt, cur, nullptr, B, d, (float*)P(c->o_hg), st));
-  }
-  // ---- prediction heads as one GEMM over the stacked weights   (gnn_transformer.py:120-126)
-  GT_TRY(gt_linear_fwd_ld(GT_F32, GT_F32, compute, P(c->o_hg), m->head_w, m->head_b, logits, B, m->Nh, d, m->ldy, 0, 0.f, 0, st));
-  // the side streams wrote into this arena: join them before anything can hand it back to the allocator
-  if (k.esort && m->st_dw) GT_TRY(gt_stream_wait_event(st, m->ev_sort[1]));
-  else if (k.want_wt && m->st_dw) GT_TRY(gt_stream_wait_event(st, m->ev_wt[1]));
-  return GT_OK;
+  return forward_encoder(m, c, logits, st);
 }
 
 // =================================================================================================================================
@@ -992,6 +1105,11 @@ int Bwd::encoder(const float* dlogits, bool frozen) const {
     GT_TRY(gt_layernorm_bwd(tdt, P(c->o_tok), nullptr, dcur, m->nin_w, (float*)P(c->o_st0), (float*)P(c->o_st0) + rows, 0.f, 0, rows, d,
                             dnext, nullptr, G + m->off_nin_w, G + m->off_nin_b, W(), ws_bytes, st));
     std::swap(dcur, dnext);
+  }
+  if (m->enc_only) {   // the cls gradient = column sums of the CLS rows; the token-row gradient stays where it is for stage 4
+    GT_TRY(gt_colsum_rows_f32(tdt, dcur, c->last_rows, B, d, G + m->off_cls, st));
+    c->dy = dcur;
+    return flush();
   }
   // ---- token rows -> node rows (+ the CLS gradient)
   const void* d_hn = Q(c->q_d_hn);
@@ -1104,10 +1222,27 @@ int Bwd::input_encoder() const {
   const int64_t N = c->in.N, D = m->D;
   const size_t ws_bytes = c->bws_bytes;
   void* d_h0 = c->d_h0;
+  int dy_dt = GT_F32;
+  if (m->enc_only && m->embed_kind == 1) {
+    // encoder-only mode, Linear encoder: the node rows' gradient = the token-row gradient stage 1 left (c->dy), scattered back to the
+    // nodes in the token type (zero rows for the nodes a truncated graph drops; the CLS rows were summed in stage 1)
+    GT_TRY(gt_seq_scatter(c->tdt, c->dy, nullptr, c->g.graph_ptr, c->g.node_graph, c->seq_desc, c->in.B, 1, 1, N, D, Q(c->q_d_hn), nullptr, st));
+    d_h0 = Q(c->q_d_hn);
+    dy_dt = c->tdt;
+  } else if (m->enc_only) {
+    // ... table encoders: every table row sums its nodes' token-row gradients through the forward's row map and sort plan; d perturb =
+    // the node's token-row gradient (zero rows for dropped nodes), written by the same call into the caller's buffer
+    GT_CHECK_ARG(c->k.esort, "backward of a forward prepared without will_bwd");
+    float* d_tabs[MAXT];
+    for (int t = 0; t < c->T; ++t) d_tabs[t] = G + m->off_tables[t];
+    GT_TRY(gt_embed_tokens_bwd(c->T, c->e_rows, c->tdt, c->dy, (const int32_t*)P(c->o_rowmap), N, D, P(c->o_eplan), d_tabs, c->in.d_perturb,
+                               W(), ws_bytes, st));
+    return flush();
+  }
   if (m->embed_kind == 1) {   // dW = d_h0^T x, db = colsum(d_h0); the features need no gradient
     const int64_t K = m->ne_K, Kp = (int64_t)c4((size_t)K);
     float* dw = Kp == K ? G + m->off_ne_w : (float*)Q(c->q_ne_dw);
-    GT_TRY(gt_linear_bwd(GT_F32, GT_F32, c->compute, c->ne_x, c->ne_w, d_h0, nullptr, nullptr, nullptr, nullptr, dw, G + m->off_ne_b, N, D, Kp,
+    GT_TRY(gt_linear_bwd(GT_F32, dy_dt, c->compute, c->ne_x, c->ne_w, d_h0, nullptr, nullptr, nullptr, nullptr, dw, G + m->off_ne_b, N, D, Kp,
                          0.f, W(), ws_bytes, st));
     if (Kp != K) GT_TRY(flush());   // the re-pitch below reads the summed gradient
     if (c->k.ov) gt_overlap_dw_sync();
@@ -1175,7 +1310,7 @@ extern "C" int gt_model_backward(const gt_model* m, void* ctx_, const float* dlo
     }
   }
   if ((stages & 2) && !frozen) {
-    GT_TRY(s.message_passing());
+    if (!m->enc_only) GT_TRY(s.message_passing());   // (encoder-only mode: the bit is accepted and does nothing)
     c->stages_done |= 2;
   }
   if ((stages & 4) && !frozen) {

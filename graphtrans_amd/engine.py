@@ -22,6 +22,10 @@ Covered configuration (everything else keeps using the module path, see `eligibl
   weight images; every parameter trainable.
   The PNA baseline (models/pna.py: `PNANet`) runs the same mode over the PNA stack, with its own heads (gt_model::head_kind,
   csrc/mlp_heads.hip): the narrow MLP (max_seq_len None) or the per-position two-layer heads (gnn_emb_dim a multiple of 16 up to 512).
+  The Transformer baseline (models/transformer.py: `Transformer`, opt-in `model.fused_step`, cls pooling) runs the driver's encoder-only
+  mode (gt_model::enc_only): no message passing, the input encoder's rows are the token rows -- ASTNodeEncoder / AtomEncoder through
+  gt_embed_tokens_*, nn.Linear in gnn2transformer's place -- then the token path's encoder, final norm and heads; every parameter
+  trainable, a perturb only with `model.fused_flag` and a table encoder, no dist.GradSync.  `model_parts` tells the families apart.
 Reference call path: trainers/base_trainer.py:29-36 -> models/gnn_transformer.py:88-127 -> modules/gnn_module.py:181-224 ->
 modules/transformer_encoder.py:42-61.
 """
@@ -64,6 +68,18 @@ def readout_kind(model):
     return POOL_KINDS[model.graph_pooling] if isinstance(model, (GNN, PNANet)) else 0
 
 
+def model_parts(model):
+    """(message-passing stack, token encoder, input encoder) of a model -- THE place that knows where each model family keeps them:
+    `gnn_node` / `transformer_encoder` / `gnn_node.node_encoder` for the four families with message passing (no token encoder in the
+    read-out mode), None / `transformer` / `node_encoder` for `models.transformer.Transformer`, which has no message passing (the
+    driver's encoder-only mode, gt_model::enc_only)."""
+    from .models.transformer import Transformer
+    if isinstance(model, Transformer):
+        return None, model.transformer, model.node_encoder
+    gnn = model.gnn_node
+    return gnn, (None if readout_kind(model) else model.transformer_encoder), gnn.node_encoder
+
+
 def head_kind(model):
     """gt_model::head_kind: 0 the linear heads, 1 the narrow MLP of `PNANet` (max_seq_len None), 2 its per-position two-layer heads"""
     from .models.pna import PNANet
@@ -99,6 +115,8 @@ class ModelDesc(C.Structure):   # gt_model
                [(k, _vp) for k in ("hid_w", "hid_b", "hid2_w", "hid2_b")] + \
                [(k, _i64) for k in ("off_hid_w", "off_hid_b", "off_hid2_w", "off_hid2_b")] + \
                [("readout", _i32), ("pad_readout_", _i32), ("pe", _vp), ("pe_rows", _i64)]
+    # gt_model::enc_only took the place of the padding word beside `readout` (same size, same offsets; the mirror keeps the field's name)
+    enc_only = property(lambda self: self.pad_readout_, lambda self, v: setattr(self, "pad_readout_", int(v)))
 
 
 class BatchDesc(C.Structure):   # gt_model_batch
@@ -206,9 +224,14 @@ class _Plan:
         _check_abi()
         lib = _lib.lib()
         self.readout = readout_kind(model)
-        gnn, enc = model.gnn_node, (None if self.readout else model.transformer_encoder)   # (read-out mode: nothing behind gnn_node but the heads)
-        self.L, self.has_vn = gnn.num_layer, isinstance(gnn, GNN_node_Virtualnode)
-        if hasattr(gnn, "layers"):   # PNANodeEmbedding
+        gnn, enc, ne = model_parts(model)   # (read-out mode: nothing behind gnn_node but the heads; encoder-only mode: no gnn_node)
+        self.enc_only = gnn is None
+        self.L, self.has_vn = (0 if gnn is None else gnn.num_layer), isinstance(gnn, GNN_node_Virtualnode)
+        if gnn is None:   # models.transformer.Transformer: the node rows are the token rows
+            self.kind = "gcn"   # (gt_model::conv is not read without conv layers)
+            self.D = enc.d_model
+            self.jk_cat = False
+        elif hasattr(gnn, "layers"):   # PNANodeEmbedding
             self.kind = "pna"
             self.D = gnn.layers[0].in_channels
             self.jk_cat = False
@@ -235,7 +258,7 @@ class _Plan:
             return [seg(p) for p in ps][0]
 
         cm = self.cm = ModelDesc()
-        ne = gnn.node_encoder
+        cm.enc_only = int(self.enc_only)
         if hasattr(ne, "type_encoder"):  # ASTNodeEncoder
             self.embed = [ne.type_encoder.weight, ne.attribute_encoder.weight, ne.depth_encoder.weight]
             self.embed_clamp = [-1, -1, int(ne.max_depth)]
@@ -260,7 +283,10 @@ class _Plan:
         cm.off_vn_emb = seg(self.vn_emb) if self.has_vn else -1
         self.w3_weights = []
         self.etab_flat = None
-        if self.kind == "pna":
+        self.conv_desc = None
+        if self.enc_only:
+            pass   # no conv descriptors, no virtual-node streams or events, no gnn2transformer
+        elif self.kind == "pna":
             self._init_pna(gnn, block)
         else:
             self._init_convs(gnn, seg, block)
@@ -342,7 +368,8 @@ class _Plan:
         self.frozen = None   # set_frozen: which parameters the backward hands gradients to
         # ---- the rest of the static struct
         cm.conv = {"gcn": 0, "gin": 1, "pna": 2}[self.kind]
-        cm.L, cm.n_enc, cm.has_vn, cm.jk_cat, cm.residual = L, len(self.enc_layers), int(self.has_vn), int(self.jk_cat), int(bool(gnn.residual))
+        cm.L, cm.n_enc, cm.has_vn, cm.jk_cat = L, len(self.enc_layers), int(self.has_vn), int(self.jk_cat)
+        cm.residual = int(bool(gnn.residual)) if gnn is not None else 0
         cm.D, cm.d, cm.Nh, cm.ldy = D, d, self.Nh, self.ldy
         cm.readout = self.readout
         cm.max_input_len = int(enc.max_input_len) if enc is not None else 0
@@ -354,7 +381,7 @@ class _Plan:
         if pe is not None:
             cm.pe, cm.pe_rows = self.pe_ptr, int(self.pe.shape[0])
         cm.vn_defer_dw = int(VN_DEFER_DW)
-        cm.conv_layers = C.cast(self.conv_desc, _vp)
+        cm.conv_layers = C.cast(self.conv_desc, _vp) if self.conv_desc is not None else None
         cm.vn = C.cast(self.vn_desc, _vp) if nvn else None
         cm.enc = C.cast(self.enc_desc, _vp) if self.enc_layers else None
         for t, w in enumerate(self.embed):
@@ -403,7 +430,7 @@ class _Plan:
             self.w3_weights.append(self.ne_lin.weight)
         self.imgs3 = self.imgs3e = self.imgs1 = None
         if w3.ENABLED:
-            if len(self.w3_weights) <= W_MAX_BOUND:
+            if self.w3_weights and len(self.w3_weights) <= W_MAX_BOUND:   # (none: the encoder-only mode with a table or a re-pitched encoder)
                 self.imgs3 = w3.W3Images(self.w3_weights)
             if self.w3_enc_weights and len(self.w3_weights) + len(self.w3_enc_weights) <= W_MAX_BOUND:
                 self.imgs3e = w3.W3Images(self.w3_weights + self.w3_enc_weights)
@@ -416,18 +443,21 @@ class _Plan:
         self.ranges = list(zip(lo, hi))
         self.cm_ref = C.byref(cm)
         # range 0 -- what stage 1 of the backward completes -- holds every parameter outside gnn_node and nothing else
+        # (encoder-only mode: what lies below the tail is the input encoder, and there is no frozen pattern)
         tail = self.ranges[0][0]
-        gnn_ids = {id(p) for p in gnn.parameters()}
+        gnn_ids = {id(p) for p in (gnn if gnn is not None else ne).parameters()}
         self.gnn_plist = [p for p, o in self.params if o < tail]
         self.tail_outside_gnn = {id(p) for p in self.gnn_plist} == gnn_ids
-        self.set_frozen(frozen_pattern(model) == "gnn")
+        self.set_frozen(gnn is not None and frozen_pattern(model) == "gnn")
 
     def _init_encoder(self, model, enc, seg, block):
-        """gnn2transformer, cls / norm_input, the encoder layers and the final norm: gradient offsets and descriptors (token path)"""
+        """gnn2transformer (not in the encoder-only mode), cls / norm_input, the encoder layers and the final norm: gradient offsets and
+        descriptors (token path, encoder-only mode)"""
         cm, d = self.cm, self.d
-        g2t = self.g2t = model.gnn2transformer
-        cm.off_g2t_w, cm.off_g2t_b = seg(g2t.weight), seg(g2t.bias)
-        self.w3_weights.append(g2t.weight)
+        if not self.enc_only:
+            g2t = self.g2t = model.gnn2transformer
+            cm.off_g2t_w, cm.off_g2t_b = seg(g2t.weight), seg(g2t.bias)
+            self.w3_weights.append(g2t.weight)
         self.cls = enc.cls_embedding
         cm.off_cls = seg(self.cls) if self.cls is not None else -1
         self.norm_in = enc.norm_input
@@ -733,12 +763,16 @@ def frozen_pattern(model):
     frozen = {id(p) for p in model.parameters() if not p.requires_grad}
     if not frozen:
         return "none"
-    return "gnn" if frozen == {id(p) for p in model.gnn_node.parameters()} else "other"
+    gnn = model_parts(model)[0]   # (a model without message passing has no "gnn" pattern)
+    return "gnn" if gnn is not None and frozen == {id(p) for p in gnn.parameters()} else "other"
 
 
 def eligible(model, batched_data, perturb):
     """True when the fused path covers this model / call (the static part is cached per model and mode)."""
     if not getattr(model, "fused", True):
+        return False
+    gnn, _, ne = model_parts(model)
+    if gnn is None and not _enc_only_call_ok(model, ne, perturb):
         return False
     # a perturbation (FLAG: forward(batched_data, perturb)) sends the model to the module path, unless `model.fused_flag` asks for the
     # fused step with it (`_perturb_ok`): opt-in, like `fused_freeze`
@@ -777,8 +811,6 @@ def eligible(model, batched_data, perturb):
     if pos is not None and not (pos.dropout.p == 0 and pos.pe.is_cuda and pos.pe.dtype == torch.float32 and pos.pe.is_contiguous()):
         return False   # (changed since the static answer was cached: the module path raises GNNTransformer._packed_pe's message)
     x = batched_data.x
-    gnn = model.gnn_node
-    ne = gnn.node_encoder
     if type(ne) is torch.nn.Linear:
         # (features that require a gradient go through the module path: the fused node only differentiates parameters)
         if not (x.is_cuda and x.dtype == torch.float32 and x.dim() == 2 and x.shape[1] == ne.in_features
@@ -795,7 +827,7 @@ def eligible(model, batched_data, perturb):
             # e.g. the reference's `--feature simple` (dataset/mol.py:65-69) slices x to 2 columns: the fused kernels
             # index one column per table, so a different column count goes through the module path
             return False
-    if hasattr(gnn, "layers"):   # PNANodeEmbedding: no edge features on its path (modules/pna/pna_module.py:73)
+    if gnn is None or hasattr(gnn, "layers"):   # no message passing / PNANodeEmbedding: no edge features on the path (modules/pna/pna_module.py:73)
         return True
     # edge features: the aggregate kernels read `edge_cols` values per edge at that pitch
     ee = gnn.convs[0].edge_encoder
@@ -810,9 +842,23 @@ def eligible(model, batched_data, perturb):
     return True
 
 
+def _enc_only_call_ok(model, ne, perturb):
+    """what `models.transformer.Transformer` asks of a call beside everything `eligible` asks of every model: the model opted in
+    (`model.fused_step`, off by default), no attached active dist.GradSync (data parallelism stays on the module path for this model,
+    DESIGN.md section 10), and a perturbation only with a table encoder (the driver refuses it with the Linear encoder)"""
+    if not getattr(model, "fused_step", False):
+        return False
+    sync = state(model).get("sync")
+    if sync is not None and sync.active:
+        return False
+    return perturb is None or type(ne) is not torch.nn.Linear
+
+
 def emb_dim(model):
-    """gnn_emb_dim: the width of the node rows, and of a perturbation"""
-    gnn = model.gnn_node
+    """gnn_emb_dim (d_model for a model without message passing): the width of the node rows, and of a perturbation"""
+    gnn, enc, _ = model_parts(model)
+    if gnn is None:
+        return int(enc.d_model)
     return int(gnn.layers[0].in_channels if hasattr(gnn, "layers") else gnn.convs[0].emb_dim)
 
 
@@ -875,9 +921,10 @@ torch.nn.modules.module.register_module_module_registration_hook(_note_ddp_wrapp
 
 
 def _frozen_ok(model):
-    """every parameter trainable, or -- only with `model.fused_freeze`, never in the read-out mode -- exactly gnn_node frozen"""
+    """every parameter trainable, or -- only with `model.fused_freeze`, never in the read-out or the encoder-only mode -- exactly
+    gnn_node frozen"""
     pat = frozen_pattern(model)
-    if readout_kind(model):
+    if readout_kind(model) or model_parts(model)[0] is None:
         return pat == "none"
     return pat == "none" or (pat == "gnn" and bool(getattr(model, "fused_freeze", False)))
 
@@ -886,7 +933,12 @@ def _eligible_static(model):
     from . import ops
     from .modules.conv import GCNConv
     from .modules.norm import BatchNorm1d
-    gnn = model.gnn_node
+    try:
+        gnn = model_parts(model)[0]
+    except Exception:
+        return False
+    if gnn is None:
+        return _eligible_static_enc_only(model)
     try:
         ro = readout_kind(model)   # models.gnn.GNN: message passing -> sum / mean / max pooling -> heads (no PNA stack, JK = last only)
     except Exception:
@@ -951,7 +1003,7 @@ def _eligible_static_rest(model):
     """what every conv kind asks of the rest of the model: node encoder, encoder widths, head dim, FFN width, synchronised BatchNorm,
     parameter dtype, frozen pattern (called inside the callers' try)"""
     from .modules.norm import BatchNorm1d, any_sync
-    ne = model.gnn_node.node_encoder
+    _, enc, ne = model_parts(model)
     if type(ne) is torch.nn.Linear:
         if ne.bias is None:
             return False
@@ -959,7 +1011,7 @@ def _eligible_static_rest(model):
         return False
     if hasattr(ne, "atom_embedding_list") and len(ne.atom_embedding_list) > 16:
         return False
-    if not readout_kind(model) and not _encoder_ok(model.transformer_encoder):
+    if enc is not None and not _encoder_ok(enc):
         return False
     # (synchronised BatchNorm -- statistics over all data-parallel ranks -- runs on this path too: the library's BatchNorm calls
     # exchange their statistics through dist.BnSyncHook, installed around the pass; all of the model's BatchNorms or none)
@@ -985,6 +1037,34 @@ def _encoder_ok(enc):
         if mod.linear1.weight.shape[0] % 8:
             return False
     return True
+
+
+def _eligible_static_enc_only(model):
+    """Transformer (models/transformer.py:20-115) on the driver's encoder-only mode: cls pooling, 1 .. MAXL encoder layers, and an input
+    encoder whose rows can be the token rows -- ASTNodeEncoder / AtomEncoder with at most 16 tables of at most 16384 rows each (the
+    sorted table backward, ops.EMBED_SORT_MAX_ROWS) and d_model columns, or nn.Linear(F, d_model) with a bias.  Every parameter
+    trainable: this mode has no frozen pattern."""
+    from .ops import EMBED_SORT_MAX_ROWS
+    try:
+        _, enc, ne = model_parts(model)
+        if model.graph_pooling != "cls" or enc.cls_embedding is None or not (1 <= len(enc.transformer.layers) <= MAXL):
+            return False
+        d = int(enc.d_model)
+        if type(ne) is torch.nn.Linear:
+            if ne.out_features != d:
+                return False
+        else:
+            if hasattr(ne, "type_encoder"):
+                tabs = [ne.type_encoder.weight, ne.attribute_encoder.weight, ne.depth_encoder.weight]
+            elif hasattr(ne, "atom_embedding_list"):
+                tabs = [e.weight for e in ne.atom_embedding_list]
+            else:
+                return False
+            if not (1 <= len(tabs) <= MAXT and all(t.dim() == 2 and t.shape[1] == d and 1 <= t.shape[0] <= EMBED_SORT_MAX_ROWS for t in tabs)):
+                return False
+        return frozen_pattern(model) == "none" and _eligible_static_rest(model)
+    except Exception:
+        return False
 
 
 def _eligible_static_pna(model):
@@ -1076,7 +1156,7 @@ class _FusedModel(torch.autograd.Function):
         cm = plan.cm
         if plan.min_elems != DW_OVERLAP_MIN_ELEMS:
             plan._set_min_elems()
-        enc, gnn = (None if plan.readout else model.transformer_encoder), model.gnn_node
+        gnn, enc, _ = model_parts(model)
         training = bool(model.training)
         bt = BatchDesc()
         x, batch = batched_data.x, batched_data.batch
@@ -1105,6 +1185,13 @@ class _FusedModel(torch.autograd.Function):
                 else:
                     bt.lay_meta = lay.meta.data_ptr()
                 keep.append(lay)
+        elif plan.enc_only:   # the batch's edges are not this model's input: the driver builds graph_ptr / node_graph from `batch` alone
+            if batch.dtype != torch.int64:
+                raise TypeError("batch must be int64 (PyG collation dtype)")
+            batch = batch.contiguous()
+            E, B = 0, _num_graphs(batched_data, sizes)
+            bt.batch = batch.data_ptr()
+            keep.append(batch)
         else:
             ei = batched_data.edge_index
             if ei.dtype != torch.int64 or batch.dtype != torch.int64:
@@ -1131,7 +1218,7 @@ class _FusedModel(torch.autograd.Function):
                 bt.node_depth, bt.depth_stride = depth.data_ptr(), (depth.stride(0) if N > 1 else 1)
                 keep.append(depth)
         ea = getattr(batched_data, "edge_attr", None)
-        mode0 = plan.conv_desc[0].edge_mode if plan.kind != "pna" else GT_EDGE_NONE
+        mode0 = plan.conv_desc[0].edge_mode if (plan.kind != "pna" and not plan.enc_only) else GT_EDGE_NONE
         if mode0 == GT_EDGE_LINEAR:
             ea = ea if (ea.dtype == torch.float32 and ea.is_contiguous()) else ea.float().contiguous()
         elif mode0 == GT_EDGE_TABLES:
@@ -1163,8 +1250,9 @@ class _FusedModel(torch.autograd.Function):
         bt.use_w1 = int(tok_bf16 and plan.imgs1 is not None)
         # dropout seeds: drawn in the module path's order (GNN first, then the encoder)
         from .modules.gnn_module import _gnn_seed
-        bt.gnn_seed = _gnn_seed(gnn) & 0xFFFFFFFFFFFFFFFF
-        bt.gnn_p = float(gnn.drop_ratio) if training else 0.0
+        if gnn is not None:
+            bt.gnn_seed = _gnn_seed(gnn) & 0xFFFFFFFFFFFFFFFF
+            bt.gnn_p = float(gnn.drop_ratio) if training else 0.0
         enc_p = float(enc.dropout_p) if enc is not None else 0.0
         bt.enc_p = enc_p if training else 0.0
         bt.enc_seed = (int(torch.empty((), dtype=torch.int64).random_().item()) & 0xFFFFFFFFFFFFFFFF) if (training and enc_p > 0) else 0

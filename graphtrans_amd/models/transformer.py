@@ -6,7 +6,7 @@ behind the reference's module surface: same ctor `(num_tasks, node_encoder, edge
 perturb=None)`, static `get_emb_dim / add_args / name`, and the same state_dict keys (`node_encoder.*`, `transformer.*`,
 `graph_pred_linear.*` or `graph_pred_linear_list.<i>.*`), so reference checkpoints load.
 
-Data paths (module path only; the whole-model driver does not know this model):
+Data paths.  The module path (the default):
   * cls: the packed token layout with CLS rows.  With `fused_embed` on and ops.embed_tokens_supported (a table encoder: ASTNodeEncoder,
     AtomEncoder) the token rows come from ops.embed_tokens, which writes them straight from the embedding tables; otherwise from
     the composition node_encoder -> + perturb -> ops.seq_gather (also the nn.Linear encoder of the TU datasets).  Then
@@ -15,6 +15,15 @@ Data paths (module path only; the whole-model driver does not know this model):
     with the UN-transformed encoder output as base -- the leading nodes a truncated graph drops keep their input rows -- then
     global_*_pool over all N rows (ops.seq_scatter, ops.graph_pool).  The packed layout: padding never influences a valid row.
 
+The fused step (opt-in: `model.fused_step = True`, or `args.fused_step`; no parser flag, like `fused_embed`; off by default): with cls
+pooling the whole forward and backward run as ONE C call per direction on the whole-model driver's encoder-only mode (engine.py,
+csrc/model.hip: gt_model::enc_only) whenever `engine.eligible` says yes -- a table encoder with at most 16 tables of at most 16384 rows,
+or nn.Linear with a bias; every parameter trainable fp32; no tensor hooks, DDP wrapper or active dist.GradSync.  A perturbation
+stays on the fused step only with `model.fused_flag` (same kind of attribute) and a table encoder: flag.flag_step then keeps all m
+passes there.  Everything else -- sum | mean | max pooling, larger tables, a perturbation with the Linear encoder, any frozen
+parameter -- falls through to the module path below, exactly as it runs without the attribute.  `fused_embed` has no meaning on the
+fused step: the driver always writes the token rows straight from the tables.
+
 Deviations from the reference:
   * graph_pooling "attention" / "set2set" raise NotImplementedError (not built, as in GNN);
   * any other pooling, "last" included, raises ValueError("Invalid graph pooling type.") -- as the reference does;
@@ -22,10 +31,10 @@ Deviations from the reference:
 """
 import torch
 
-from .. import ops
+from .. import engine, ops
 from ..modules.gnn_module import _encode_nodes, batch_structure
 from ..modules.transformer_encoder import TransformerNodeEncoder
-from .base_model import BaseModel, stacked_heads
+from .base_model import BaseModel, StackedHeads, stacked_heads
 
 POOLINGS = ("cls", "sum", "mean", "max")
 POOLINGS_NOT_BUILT = ("attention", "set2set")
@@ -64,6 +73,9 @@ class Transformer(BaseModel):
         self.max_seq_len = args.max_seq_len
         # token rows straight from the embedding tables (ops.embed_tokens) where the encoder is a sum of tables; off: the composition
         self.fused_embed = bool(getattr(args, "fused_embed", FUSED_EMBED_DEFAULT))
+        # the whole step on the driver's encoder-only mode where engine.eligible allows it (cls pooling); `fused_flag`: with a perturbation too
+        self.fused_step = bool(getattr(args, "fused_step", False))
+        self.fused_flag = bool(getattr(args, "fused_flag", False))
         if self.max_seq_len is None:
             self.graph_pred_linear = torch.nn.Linear(self.emb_dim, self.num_tasks)
         else:
@@ -88,6 +100,11 @@ class Transformer(BaseModel):
             raise ValueError("empty batch")
         if perturb is not None and perturb.shape[0] != batched_data.batch.numel():
             raise ValueError("perturb must have one row per node")
+        if self.fused_step and engine.eligible(self, batched_data, perturb):   # whole model as one autograd node (engine.py)
+            out = engine.forward(self, batched_data, perturb)
+            if self.max_seq_len is None:
+                return out
+            return StackedHeads(out.view(out.shape[0], self.max_seq_len, self.num_tasks))
         enc = self.transformer
         gs = batch_structure(batched_data)
         max_len = int(enc.max_input_len)

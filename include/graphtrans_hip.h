@@ -1191,8 +1191,18 @@ typedef struct gt_model {
    * [Nh][D]; the PNA baseline, models/pna.py:94-104, with head_kind 1 or 2).  Requires n_enc == 0, jk_cat == 0, no pe, any conv kind
    * (GT_CONV_PNA under its own conditions above), gt_model_batch::gnn_frozen == 0; g2t / cls / norm / enc fields
    * and w3_enc / w1 are not read, no token layout is built (gt_model_sizes: rows = num_work = 0) and no staging-ring slot is taken.
-   * (In front of {pe, pe_rows}, which stay the struct's tail.) */
-  int32_t readout, pad_readout_;
+   * (In front of {pe, pe_rows}, which stay the struct's tail.)
+   * enc_only != 0: the encoder-only mode (the plain Transformer baseline, models/transformer.py:87-101) -- no message passing at all: L == 0,
+   * no conv layers, no virtual node, no gnn2transformer, D == d.  The input encoder's rows ARE the token rows: the table encoders
+   * (embed_kind 0 / 2) write them straight into the token matrix (gt_seq_token_rows + gt_embed_tokens_fwd, gt_model_batch::perturb as
+   * the kernel's row operand), the Linear encoder (embed_kind 1) stands where gnn2transformer stands on the token path (GEMM into
+   * [N][d] token-type rows, then gt_seq_gather_cls32); behind the token rows the step is the token path's.  Requires L == 0, n_enc >= 1,
+   * with_cls, readout == 0, jk_cat == 0, has_vn == 0, pe == NULL, head_kind == 0, D == d, tables of at most 16384 rows (embed_sorted);
+   * conv_layers / vn / g2t_* / w3 jobs of conv weights are not read.  Only graph_ptr / node_graph of the structure are read: without a
+   * caller's structure the driver runs gt_graph_prep at E = 0 (gt_model_batch::edge_index may be NULL, E is ignored).  L == 0 is legal
+   * ONLY in this mode.  gt_model_batch::gnn_frozen, and perturb with embed_kind == 1, are refused (GT_ERR_INVALID_ARG, nothing launched).
+   * (The field took the place of the padding word beside `readout`: the struct's size and every other offset are unchanged.) */
+  int32_t readout, enc_only;
   /* PositionalEncoding (models/gnn_transformer.py:149-168) or NULL: the module's `pe` buffer read as [pe_rows][d] fp32, 16-byte aligned,
    * pe_rows >= max_input_len.  The token row of the node at padded position p (gt_seq_positions) gets + pe[p], in fp32, before its one
    * rounding to the token type; CLS rows get nothing; no gradient. */
@@ -1258,12 +1268,17 @@ int gt_model_forward(const gt_model* model, void* ctx, void* arena, float* logit
  * With gt_model_batch::gnn_frozen the backward IS stage 1: gnn2transformer contributes its weight / bias gradient only (no dX GEMM),
  * the stage closes the backward itself (deferred sums flushed, overlap stream joined) and nothing is enqueued on the virtual-node
  * stream; only the range {off_g2t_w .. grad_total} of `grads` is written (range 0 of gt_model_grad_ranges, which does not change).
- * Bits 1 and 2 are then accepted -- in the same call (stages = 7) or in later ones -- and do nothing. */
+ * Bits 1 and 2 are then accepted -- in the same call (stages = 7) or in later ones -- and do nothing.
+ * With gt_model::enc_only: bit 0 runs heads, final norm, encoder layers, norm_input and the CLS embedding's gradient (column sums of the
+ * CLS rows) and leaves the token-row gradient in the backward arena; bit 1 is accepted and does nothing; bit 2 turns the token-row
+ * gradient into the input encoder's gradients (gt_embed_tokens_bwd through the forward's row map and sort plan, d_perturb as its d_add;
+ * or gt_seq_scatter + the Linear encoder's dW / db) and closes the backward. */
 int gt_model_backward(const gt_model* model, void* ctx, const float* dlogits, float* grads, void* barena, int stages,
                       gt_stream_t stream);
 /* first / one-past-last float of the gradient range each stage completes: {g2t..total, gnn_lo..g2t, 0..gnn_lo}; with
  * gt_model::readout (no gnn2transformer) the heads' offset stands where g2t does: {heads..total, gnn_lo..heads, 0..gnn_lo}, heads =
- * off_head_w, or off_hid_w (the hidden layers lead the head block) with gt_model::head_kind != 0 */
+ * off_head_w, or off_hid_w (the hidden layers lead the head block) with gt_model::head_kind != 0; with gt_model::enc_only the middle
+ * range is empty: {tail..total, tail..tail, 0..tail}, tail = off_cls, the first float behind the input encoder's block */
 int gt_model_grad_ranges(const gt_model* model, int64_t* lo3, int64_t* hi3);
 /* out4 = sizeof {gt_model, gt_model_batch, gt_image_set, gt_stage_ring}: a binding checks its mirror of the layouts */
 int gt_model_abi_sizes(int64_t* out4);

@@ -12,9 +12,15 @@ variants alternating, all warmed up first; token stream bf16 (`mixed`) or fp32. 
 forward.  Device events around `--steps` steps, `--reps` times for every variant: one JSON line per (workload, mode) with the ms/step of
 every repetition, graphs/s at the median, the spread of identical runs ((max - min) / median) and composition / fused.
 
-    python tools/transformer_baseline_bench.py [--steps 50] [--reps 5] [--workloads code2,molpcba,nci1] [--modes mixed,fp32]
+`--fused_step` adds a third variant to the alternation, `step`: the same model with `fused_step` on (and `fused_flag` under
+`--perturb`; the Linear encoder keeps the module path with a perturbation), i.e. the whole step as one call per direction on the
+whole-model driver.  Its baseline is the default module path in the same process (`fused`; `composition` for nci1):
+`step_over_off` = ms/step of `step` / ms/step of that baseline at the medians.
 
-Kernel times come from a separate run under the profiler (kernel trace + statistics) of, e.g., `--workloads code2 --reps 1`.
+    python tools/transformer_baseline_bench.py [--steps 50] [--reps 5] [--workloads code2,molpcba,nci1] [--modes mixed,fp32] [--fused_step]
+
+Kernel times and launch counts come from a separate run under the profiler (kernel trace + statistics) of ONE variant, e.g.
+`--workloads code2 --modes mixed --reps 1 --fused_step --variants step`.
 """
 import argparse
 import copy
@@ -88,6 +94,8 @@ def main():
     ap.add_argument("--workloads", default="code2,molpcba,nci1")
     ap.add_argument("--modes", default="mixed,fp32")
     ap.add_argument("--perturb", action="store_true", help="a FLAG perturbation in every forward")
+    ap.add_argument("--fused_step", action="store_true", help="add the variant with model.fused_step on (the whole-model driver)")
+    ap.add_argument("--variants", default="", help="run only these variants (comma list of fused,composition,step): profiler runs")
     opt = ap.parse_args()
     from graphtrans_amd import ops
     for workload in opt.workloads.split(","):
@@ -99,6 +107,13 @@ def main():
             models = {"fused": fused, "composition": copy.deepcopy(fused)}
             models["fused"].fused_embed, models["composition"].fused_embed = True, False
             order = ("fused", "composition") if workload != "nci1" else ("composition",)   # (no tables: one variant, repeated)
+            base = order[0]   # `fused_step` off with everything else at its default: today's path
+            if opt.fused_step:
+                models["step"] = copy.deepcopy(fused)
+                models["step"].fused_step = models["step"].fused_flag = True
+                order = order + ("step",)
+            if opt.variants:
+                order = tuple(k for k in order if k in opt.variants.split(","))
             batches = [attach_sizes(gen(s)).to(DEV) for s in range(8)]
             perturbs = None
             if opt.perturb:
@@ -115,8 +130,10 @@ def main():
                        perturb=bool(opt.perturb), **{k + "_ms": [round(v, 4) for v in ms[k]] for k in order},
                        **{k + "_graphs_per_s": round(B / med[k] * 1e3, 1) for k in order},
                        spread={k: round((max(v) - min(v)) / med[k], 4) for k, v in ms.items()})
-            if "fused" in med:
+            if "fused" in med and "composition" in med:
                 res["composition_over_fused"] = round(med["composition"] / med["fused"], 4)
+            if "step" in med and base in med:
+                res["step_over_off"] = round(med["step"] / med[base], 4)
             print(json.dumps(res), flush=True)
 
 
