@@ -1,5 +1,6 @@
-"""The composite layer entry points of csrc/layers.hip (gt_encoder_layer[_pooled]_*, gt_gcn_layer_*, gt_gin_layer_*, gt_vn_update_*) as a
-record of what they do, through graphtrans_amd/layers.py and ctypes:
+"""The composite layer entry points of csrc/layers.hip (gt_encoder_layer[_pooled]_*, gt_gcn_layer_*, gt_vn_update_*; of gt_gin_layer_*
+the buffer sizes only) as a record of what they do, through graphtrans_amd/layers.py and ctypes.  Their VALUES, gt_gin_layer_fwd / _bwd
+included, are checked against float64 references in tests/test_hip_layer_references.py.  Here:
 
   - which GEMM kernels each forward and backward launches, in order (the launch profiler's labels, mask 32, as in
     tests/test_hip_linear_dispatch.py): a changed row is a changed behaviour;

@@ -162,18 +162,8 @@ def test_batchnorm_fused_dropout(rows, D, relu):
     assert torch.equal(ye, ye0)
 
 
-def _bn_keep_mask(rows, D, p, seed):
-    """the kept set of the BatchNorm dropout (csrc/norm.hip: bn_hash of (seed, row, column) >= p * 2^32), restated with int64 tensors"""
-    M = 0xFFFFFFFF
-    r = torch.arange(rows, dtype=torch.int64).reshape(-1, 1)
-    c = torch.arange(D, dtype=torch.int64).reshape(1, -1)
-    s0, s1 = seed & M, (seed >> 32) & M
-    x = (((r * 0x9E3779B1) & M) + s0 & M) ^ (((c * 0x85EBCA77) & M) + s1 & M)
-    x = x ^ (x >> 16); x = (x * 0x7feb352d) & M
-    x = x ^ (x >> 15); x = (x * 0x846ca68b) & M
-    x = x ^ (x >> 16)
-    thr = min(max(int(p * 4294967296.0), 1), 4294967295)
-    return x >= thr
+# the kept set of the BatchNorm dropout (csrc/norm.hip: bn_hash of (seed, row, column) >= p * 2^32): stated once, in tests/layer_refs.py
+from layer_refs import keep_mask_rc as _bn_keep_mask  # noqa: E402
 
 
 
