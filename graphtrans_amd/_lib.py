@@ -249,6 +249,10 @@ SIGNATURES = {
     "gt_attn_fwd": (_i, [_i, _p, _p, _p, _i64, _i64, _i, _p, _i64, _i64, _i64, _p, _i64, _p, _p, _f, _f, _f, _u64, _p]),
     "gt_attn_bwd": (_i, [_i, _p, _p, _p, _p, _p, _p, _i64, _i64, _i, _p, _i64, _i64, _i64, _p, _i64, _p, _p, _f, _f, _f,
                          _u64, _p]),
+    "gt_adj_mask_bits": (_i, [_p, _p, _p, _i64, _i64, _i64, _i64, _p, _i, _p, _p]),
+    "gt_attn_fwd_bits": (_i, [_i, _p, _p, _p, _i64, _i64, _i, _p, _i64, _i64, _i64, _p, _i64, _p, _i64, _f, _f, _f, _u64, _p]),
+    "gt_attn_bwd_bits": (_i, [_i, _p, _p, _p, _p, _p, _p, _i64, _i64, _i, _p, _i64, _i64, _i64, _p, _i64, _p, _i64, _f, _f, _f,
+                              _u64, _p]),
 }
 
 _lib = None

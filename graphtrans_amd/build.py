@@ -12,7 +12,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 INCLUDE = os.path.join(os.path.dirname(HERE), "include")
 LIB = os.path.join(HERE, "libgraphtrans_hip.so")
-SOURCES = ["common.hip", "graph_prep.hip", "aggregate.hip", "segment.hip", "graph_pool.hip", "attention.hip", "norm.hip", "linear.hip", "mlp_heads.hip", "layers.hip", "model.hip", "pna.hip", "embed.hip", "xent.hip", "optim.hip", "util.hip", "collate.hip", "flag.hip", "metrics.hip"]
+SOURCES = ["common.hip", "graph_prep.hip", "adj_mask.hip", "aggregate.hip", "segment.hip", "graph_pool.hip", "attention.hip", "norm.hip", "linear.hip", "mlp_heads.hip", "layers.hip", "model.hip", "pna.hip", "embed.hip", "xent.hip", "optim.hip", "util.hip", "collate.hip", "flag.hip", "metrics.hip"]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wall", "-Wno-unused-function"]
 
 

@@ -71,6 +71,10 @@ struct AttnArgs {
   // FILLED with mask_fill (masked_fill semantics: finite value, no gradient through the score)
   const float* dense_mask;  // [num_seqs][npos][npos]
   const float* key_valid;   // [num_seqs][npos]
+  // the same predicate as bits (csrc/adj_mask.hip): keep_bits [num_seqs][bits_T][bits_W] uint32, key k = bit k & 31 of word k >> 5
+  // (= bit k & 7 of byte k >> 3), 0 = filled, key_valid already folded in; every sequence has npos <= bits_T
+  const uint32_t* keep_bits;
+  int bits_T, bits_W;
   float mask_fill2;         // mask_value * log2(e)
   int64_t rows, d_model, row_stride;
   int nhead;
@@ -91,6 +95,27 @@ __device__ __forceinline__ bool dense_masked(const AttnArgs& a, int seq, int qpo
   if (a.key_valid && a.key_valid[(int64_t)seq * npos + kp] == 0.f) return true;
   if (a.dense_mask && a.dense_mask[((int64_t)seq * npos + qpos) * npos + kp] == 0.f) return true;
   return false;
+}
+// The same predicate from keep_bits (a kernel-argument uniform choice inside the DENSE instantiations).  A sequence's rows start at a
+// wave-uniform address; what a lane adds is a 32-bit offset (bits_T <= 65536: at most 2^29 bytes per sequence, check_bits).
+// masked_either: one (query, key) from whichever form the launch carries -- dK / dV, whose lanes walk queries.  Both forms are ONE
+// 32-bit load at base + ((seq * rows + qpos) * pitch + col) * 4 with wave-uniform base, rows and pitch (dense: the float of key kp,
+// rows = pitch = npos; bits: the word kp >> 5, rows = bits_T, pitch = bits_W), so the bits cost the instantiation no register beyond
+// the float path's.  qpos, kp < npos <= bits_T.  A float is 0 (either sign) iff its low 31 bits are.
+__device__ __forceinline__ bool masked_either(const AttnArgs& a, int seq, int qpos, int kp, int npos) {
+  const bool ub = a.keep_bits != nullptr;
+  if (!ub && a.key_valid && a.key_valid[(int64_t)seq * npos + kp] == 0.f) return true;
+  if (!ub && !a.dense_mask) return false;
+  const uint32_t* base = ub ? a.keep_bits : reinterpret_cast<const uint32_t*>(a.dense_mask);
+  const int rows = ub ? a.bits_T : npos, pitch = ub ? a.bits_W : npos;
+  const uint32_t v = base[((int64_t)seq * rows + qpos) * pitch + (ub ? kp >> 5 : kp)];
+  return ub ? !((v >> (kp & 31)) & 1u) : (v & 0x7fffffffu) == 0u;
+}
+// bits_byte: forward and dQ, where a lane owns the 8 consecutive keys k8 + i of ONE query per key step -- one byte of that query's
+// row, loaded once (k8 is a multiple of 8 below npos, so the byte lies inside the row: npos <= bits_T <= 32 * bits_W)
+__device__ __forceinline__ uint32_t bits_byte(const AttnArgs& a, int seq, int qp, int k8) {
+  const uint8_t* rows = reinterpret_cast<const uint8_t*>(a.keep_bits + (int64_t)seq * a.bits_T * a.bits_W);
+  return rows[(uint32_t)(qp * (a.bits_W * 4) + (k8 >> 3))];
 }
 
 // (sequence, 64-row tile, head) of this block.  Work-list launches are 1-D and XCD-aware: workgroup b
@@ -408,11 +433,16 @@ __global__ void __launch_bounds__(ATT_THREADS, 2) k_attn_fwd(AttnArgs a) {
       for (int i = 0; i < 8; ++i) mt = fmaxf(mt, s[i]);
       mt *= a.scale_log2;
     } else {
+      // keep-bits: the lane's 8 keys of this step are ONE byte of its query's row (loaded where the float masks are read, so the
+      // instantiation's register peak stays the float path's)
+      const bool use_bits = a.keep_bits != nullptr;
+      uint32_t kb = 0;
+      if (use_bits && qvalid) kb = bits_byte(a, seq, qp, k0 + g * 8);
 #pragma unroll
       for (int i = 0; i < 8; ++i) {
         const int kp = k0 + g * 8 + i;
         s[i] = (kp >= kv_off && kp < kv_end) ? s[i] * a.scale_log2 : -INFINITY;
-        if (qvalid && kp < npos && dense_masked(a, seq, qp, kp, npos)) s[i] = a.mask_fill2;
+        if (qvalid && kp < npos && (use_bits ? !((kb >> i) & 1u) : dense_masked(a, seq, qp, kp, npos))) s[i] = a.mask_fill2;
         mt = fmaxf(mt, s[i]);
       }
     }
@@ -539,9 +569,28 @@ __global__ void __launch_bounds__(ATT_THREADS, 2) k_attn_bwd_dq(AttnArgs a) {
   stg.load(k_first, kv_off, kv_end);
   stg.template store<TO>(sKb[0], sVb[0]);
   __syncthreads();
+  int q_wave = 0;   // the wave's first query, as a scalar (keep-bits only)
+  if constexpr (DENSE) q_wave = __builtin_amdgcn_readfirstlane(q_base + wid * 16);
   int cur = 0;
   for (int k0 = k_first; k0 < kv_end; k0 += TILE, cur ^= 1) {
     const bool more = k0 + TILE < kv_end;
+    // keep-bits: a lane's 8 keys k0 + g * 8 + i of its query are ONE byte of the query's row (query 0 for a lane without a query:
+    // loaded, never used).  It is fetched in front of the step's K / V prefetch (vmcnt retires in order: the byte does not wait for
+    // the prefetch) and turned into eight lane predicates at once.  Those live in scalar registers; the byte itself, or its
+    // per-lane offset, carried in a vector register costs the instantiations on the edge of an occupancy tier (bf16 head dim 16 at
+    // 72 registers, fp32 head dim 64 at 128) a wave.  The step waits for the byte here, once, where the float masks wait eight times.
+    const bool use_bits = DENSE && a.keep_bits != nullptr;
+    bool bit_filled[8] = {};
+    if (use_bits) {
+      // (for the same reason the lane's place in the wave is taken from mbcnt HERE, with the step's k0 / 8 as its base: a value
+      // the compiler cannot hoist out of the loop, so no per-lane offset stays in a register from step to step)
+      const uint32_t k8 = (uint32_t)k0 >> 3;
+      const uint32_t ln = __builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, k8)) - k8;   // == lane
+      const int q = q_wave + (int)(ln & 15u);
+      const uint32_t kb = bits_byte(a, seq, q < npos ? q : 0, k0 + (int)(ln >> 4) * 8);
+#pragma unroll
+      for (int i = 0; i < 8; ++i) bit_filled[i] = !((kb >> i) & 1u);
+    }
     if (more) stg.load(k0 + TILE, kv_off, kv_end);
     const LT* sK = sKb[cur];
     const LT* sV = sVb[cur];
@@ -576,7 +625,8 @@ __global__ void __launch_bounds__(ATT_THREADS, 2) k_attn_bwd_dq(AttnArgs a) {
           ds[i] = fast_exp2(e) * dd;
         } else {
           const bool kvalid = kp >= kv_off && kp < kv_end;
-          const bool filled = qvalid && kvalid && kp < npos && dense_masked(a, seq, qp, kp, npos);
+          const bool filled = qvalid && kvalid && kp < npos &&
+                              (use_bits ? bit_filled[i] : dense_masked(a, seq, qp, kp, npos));
           const float p = kvalid ? fast_exp2(((filled ? a.mask_fill2 : c[r] * a.scale_log2) - lse) - logl) : 0.f;
           ds[i] = filled ? 0.f : p * dd;  // masked_fill: no gradient through a filled score
         }
@@ -734,7 +784,7 @@ __global__ void __launch_bounds__(ATT_THREADS, (dkv_blocks_per_cu<T, HD, SP>()))
         if constexpr (!DENSE) {
           p = ok ? fast_exp2(fmaf(c[r], a.scale_log2, a0)) : 0.f;   // slot 0 holds -(max + log2 sum) here
         } else {
-          filled = ok && dense_masked(a, seq, qpos, kp, npos);
+          filled = ok && masked_either(a, seq, qpos, kp, npos);
           p = ok ? fast_exp2(((filled ? a.mask_fill2 : c[r] * a.scale_log2) - a0) - sLogl[qi]) : 0.f;
         }
         float dd, pdrop = p;   // kept weights stay unscaled in pd: 1 / keep is applied to dV once, at the end
@@ -793,6 +843,17 @@ int check_attn(const char* fn, int dtype, int64_t d_model, int nhead, int64_t nu
   return GT_OK;
 }
 
+// the bit rows are pitched by bits_T, not by npos: every sequence must fit (max_npos bounds every npos of the layout)
+int check_bits(const char* fn, const uint32_t* keep_bits, int64_t bits_T, int64_t max_npos) {
+  if (!keep_bits || bits_T <= 0) { gt_set_error("%s: keep_bits is NULL or bits_T <= 0", fn); return GT_ERR_INVALID_ARG; }
+  if (bits_T > 65536) { gt_set_error("%s: bits_T %lld unsupported (at most 65536 keys)", fn, (long long)bits_T); return GT_ERR_UNSUPPORTED; }
+  if (max_npos > bits_T) {
+    gt_set_error("%s: a sequence of %lld positions does not fit keep_bits rows of %lld keys", fn, (long long)max_npos, (long long)bits_T);
+    return GT_ERR_UNSUPPORTED;
+  }
+  return GT_OK;
+}
+
 AttnArgs make_args(const void* qkv, const void* ctx, const void* d_ctx, float* lse, float* delta, void* out,
                    int64_t rows, int64_t d_model, int nhead, const int32_t* desc, const int32_t* work,
                    int64_t row_stride, float scale, float dropout_p, uint64_t seed, const float* dense_mask,
@@ -835,8 +896,8 @@ extern "C" int gt_attn_head_dim_ok(int dtype, int64_t d_model, int nhead) {
 static int attn_fwd_impl(int pooled, int dtype, const void* qkv, void* ctx, float* lse, int64_t total_rows, int64_t d_model,
                            int nhead, const int32_t* seq_desc, int64_t num_seqs, int64_t row_stride,
                            int64_t max_npos, const int32_t* work_items, int64_t num_work, const float* dense_mask,
-                           const float* key_valid, float mask_value, float scale, float dropout_p, uint64_t seed,
-                           gt_stream_t stream_) {
+                           const float* key_valid, const uint32_t* keep_bits, int64_t bits_T, float mask_value, float scale,
+                           float dropout_p, uint64_t seed, gt_stream_t stream_) {
   int rc = check_attn("gt_attn_fwd", dtype, d_model, nhead, num_seqs, max_npos, dropout_p);
   if (rc) return rc;
   GT_CHECK_ARG(qkv && ctx && lse && seq_desc, "null buffer");
@@ -849,10 +910,11 @@ static int attn_fwd_impl(int pooled, int dtype, const void* qkv, void* ctx, floa
   a.num_work = (int)num_work;
   a.work_per_xcd = (int)gt_cdiv(num_work, 8);
   a.last_only = pooled;
+  a.keep_bits = keep_bits; a.bits_T = (int)bits_T; a.bits_W = (int)gt_cdiv(bits_T, 32);
   dim3 grid = (work_items && !pooled) ? dim3((unsigned)(8 * a.work_per_xcd * nhead), 1, 1)
                                       : dim3(pooled ? 1u : (unsigned)gt_cdiv(max_npos, BLOCK_N), (unsigned)nhead, (unsigned)num_seqs);
   const int hd = (int)(d_model / nhead);
-  const bool dense_launch = dense_mask != nullptr || key_valid != nullptr;
+  const bool dense_launch = dense_mask != nullptr || key_valid != nullptr || keep_bits != nullptr;
 #define GT_LAUNCH(T, HD)                                                                                     \
   do {                                                                                                       \
     if (dense_launch) hipLaunchKernelGGL((k_attn_fwd<T, HD, true>), grid, dim3(ATT_THREADS), 0, stream, a);  \
@@ -877,22 +939,34 @@ extern "C" int gt_attn_fwd(int dtype, const void* qkv, void* ctx, float* lse, in
                            const float* key_valid, float mask_value, float scale, float dropout_p, uint64_t seed,
                            gt_stream_t stream_) {
   return attn_fwd_impl(0, dtype, qkv, ctx, lse, total_rows, d_model, nhead, seq_desc, num_seqs, row_stride, max_npos, work_items, num_work,
-                       dense_mask, key_valid, mask_value, scale, dropout_p, seed, stream_);
+                       dense_mask, key_valid, nullptr, 0, mask_value, scale, dropout_p, seed, stream_);
+}
+// gt_attn_fwd with the masked_fill predicate as bits (gt_adj_mask_bits: key_valid folded in): the DENSE instantiations, one byte per
+// lane and key step instead of eight floats
+extern "C" int gt_attn_fwd_bits(int dtype, const void* qkv, void* ctx, float* lse, int64_t total_rows, int64_t d_model,
+                                int nhead, const int32_t* seq_desc, int64_t num_seqs, int64_t row_stride,
+                                int64_t max_npos, const int32_t* work_items, int64_t num_work, const uint32_t* keep_bits,
+                                int64_t bits_T, float mask_value, float scale, float dropout_p, uint64_t seed,
+                                gt_stream_t stream_) {
+  int rc = check_bits("gt_attn_fwd_bits", keep_bits, bits_T, max_npos);
+  if (rc) return rc;
+  return attn_fwd_impl(0, dtype, qkv, ctx, lse, total_rows, d_model, nhead, seq_desc, num_seqs, row_stride, max_npos, work_items, num_work,
+                       nullptr, nullptr, keep_bits, bits_T, mask_value, scale, dropout_p, seed, stream_);
 }
 // the 64-row tile that holds the LAST position of every sequence only (ctx / lse rows outside those tiles are not written)
 extern "C" int gt_attn_fwd_last(int dtype, const void* qkv, void* ctx, float* lse, int64_t total_rows, int64_t d_model,
                                 int nhead, const int32_t* seq_desc, int64_t num_seqs, int64_t row_stride, int64_t max_npos,
                                 float scale, float dropout_p, uint64_t seed, gt_stream_t stream_) {
   return attn_fwd_impl(1, dtype, qkv, ctx, lse, total_rows, d_model, nhead, seq_desc, num_seqs, row_stride, max_npos, nullptr, 0,
-                       nullptr, nullptr, 0.f, scale, dropout_p, seed, stream_);
+                       nullptr, nullptr, nullptr, 0, 0.f, scale, dropout_p, seed, stream_);
 }
 
 static int attn_bwd_impl(int pooled, int dtype, const void* qkv, const void* ctx, const void* d_ctx, const float* lse,
                            float* delta, void* d_qkv, int64_t total_rows, int64_t d_model, int nhead,
                            const int32_t* seq_desc, int64_t num_seqs, int64_t row_stride, int64_t max_npos,
                            const int32_t* work_items, int64_t num_work, const float* dense_mask,
-                           const float* key_valid, float mask_value, float scale, float dropout_p, uint64_t seed,
-                           gt_stream_t stream_) {
+                           const float* key_valid, const uint32_t* keep_bits, int64_t bits_T, float mask_value, float scale,
+                           float dropout_p, uint64_t seed, gt_stream_t stream_) {
   int rc = check_attn("gt_attn_bwd", dtype, d_model, nhead, num_seqs, max_npos, dropout_p);
   if (rc) return rc;
   GT_CHECK_ARG(qkv && ctx && d_ctx && lse && delta && d_qkv && seq_desc, "null buffer");
@@ -904,6 +978,7 @@ static int attn_bwd_impl(int pooled, int dtype, const void* qkv, const void* ctx
                          work_items, row_stride, scale, dropout_p, seed, dense_mask, key_valid, mask_value);
   a.num_work = (int)num_work;
   a.work_per_xcd = (int)gt_cdiv(num_work, 8);
+  a.keep_bits = keep_bits; a.bits_T = (int)bits_T; a.bits_W = (int)gt_cdiv(bits_T, 32);
   dim3 grid = work_items ? dim3((unsigned)(8 * a.work_per_xcd * nhead), 1, 1)
                          : dim3((unsigned)gt_cdiv(max_npos, BLOCK_N), (unsigned)nhead, (unsigned)num_seqs);
   // pooled: dQ for the last tile of every sequence (a block per sequence and head), dK / dV for every key tile with the query loop cut
@@ -916,7 +991,7 @@ static int attn_bwd_impl(int pooled, int dtype, const void* qkv, const void* ctx
     a.q_last_only = 1;
   }
   const int hd = (int)(d_model / nhead);
-  const bool dense_launch = dense_mask != nullptr || key_valid != nullptr;
+  const bool dense_launch = dense_mask != nullptr || key_valid != nullptr || keep_bits != nullptr;
 #define GT_LAUNCH(T, HD)                                                                        \
   do {                                                                                          \
     if (dense_launch) {                                                                         \
@@ -952,7 +1027,17 @@ extern "C" int gt_attn_bwd(int dtype, const void* qkv, const void* ctx, const vo
                            const float* key_valid, float mask_value, float scale, float dropout_p, uint64_t seed,
                            gt_stream_t stream_) {
   return attn_bwd_impl(0, dtype, qkv, ctx, d_ctx, lse, delta, d_qkv, total_rows, d_model, nhead, seq_desc, num_seqs, row_stride, max_npos,
-                       work_items, num_work, dense_mask, key_valid, mask_value, scale, dropout_p, seed, stream_);
+                       work_items, num_work, dense_mask, key_valid, nullptr, 0, mask_value, scale, dropout_p, seed, stream_);
+}
+extern "C" int gt_attn_bwd_bits(int dtype, const void* qkv, const void* ctx, const void* d_ctx, const float* lse,
+                                float* delta, void* d_qkv, int64_t total_rows, int64_t d_model, int nhead,
+                                const int32_t* seq_desc, int64_t num_seqs, int64_t row_stride, int64_t max_npos,
+                                const int32_t* work_items, int64_t num_work, const uint32_t* keep_bits, int64_t bits_T,
+                                float mask_value, float scale, float dropout_p, uint64_t seed, gt_stream_t stream_) {
+  int rc = check_bits("gt_attn_bwd_bits", keep_bits, bits_T, max_npos);
+  if (rc) return rc;
+  return attn_bwd_impl(0, dtype, qkv, ctx, d_ctx, lse, delta, d_qkv, total_rows, d_model, nhead, seq_desc, num_seqs, row_stride, max_npos,
+                       work_items, num_work, nullptr, nullptr, keep_bits, bits_T, mask_value, scale, dropout_p, seed, stream_);
 }
 // backward of gt_attn_fwd_last: d_ctx is non-zero only in the last position of every sequence; d_qkv must be ZERO-FILLED by the caller
 // (dQ is written for the last 64-row tiles only); work_items: the full attention work list (key tiles)
@@ -961,5 +1046,5 @@ extern "C" int gt_attn_bwd_last(int dtype, const void* qkv, const void* ctx, con
                                 int64_t row_stride, int64_t max_npos, const int32_t* work_items, int64_t num_work, float scale,
                                 float dropout_p, uint64_t seed, gt_stream_t stream_) {
   return attn_bwd_impl(1, dtype, qkv, ctx, d_ctx, lse, delta, d_qkv, total_rows, d_model, nhead, seq_desc, num_seqs, row_stride, max_npos,
-                       work_items, num_work, nullptr, nullptr, 0.f, scale, dropout_p, seed, stream_);
+                       work_items, num_work, nullptr, nullptr, nullptr, 0, 0.f, scale, dropout_p, seed, stream_);
 }

@@ -12,6 +12,8 @@ forward() picks between two equivalent data paths:
              row of the position pad_batch would have put it at (graph.SeqLayout.positions).
   * padded  (the reference layout (S,B,d), exact for `mean` pooling which sums padded rows,
              gnn_transformer.py:117): pad_batch -> [pos_encoder] -> [masked encoder] -> encoder.
+             The masked encoder's mask is the batch's `adj_list` when it carries one (the reference's host arrays, dense path),
+             else keep-bits built on the device from its edges (ops.adjacency_bits; `adj_self_loops` = the reference's np.eye).
 """
 import math
 
@@ -84,6 +86,8 @@ class GNNTransformer(BaseModel):
         self.masked_transformer_encoder = MaskedOnlyTransformerEncoder(args)
         self.num_encoder_layers = args.num_encoder_layers
         self.num_encoder_layers_masked = args.num_encoder_layers_masked
+        # a batch without adj_list derives the masked encoder's mask from edge_index; True = the reference's `+ np.eye` (data/adj_list.py)
+        self.adj_self_loops = bool(getattr(args, "adj_self_loops", True))
 
         self.num_tasks = num_tasks
         self.pooling = args.graph_pooling
@@ -157,7 +161,7 @@ class GNNTransformer(BaseModel):
             transformer_out = padded_h_node
             if self.pos_encoder is not None:
                 transformer_out = self.pos_encoder(transformer_out)
-            if self.num_encoder_layers_masked > 0:
+            if self.num_encoder_layers_masked > 0 and hasattr(batched_data, "adj_list"):
                 adj_list = batched_data.adj_list
                 padded_adj_list = torch.zeros((len(adj_list), max_num_nodes, max_num_nodes), device=h_node.device)
                 for idx, adj_list_item in enumerate(adj_list):  # top-left placement, as the reference (:104-107)
@@ -166,6 +170,15 @@ class GNNTransformer(BaseModel):
                 transformer_out = self.masked_transformer_encoder(
                     transformer_out.transpose(0, 1), attn_mask=padded_adj_list, valid_input_mask=src_padding_mask
                 ).transpose(0, 1)
+            elif self.num_encoder_layers_masked > 0:
+                # no host-side adj_list (data/adj_list.py): the same mask from the batch's own edges, as bits, once for all masked
+                # layers.  src_padding_mask is folded in exactly as the dense path passes it (True = padding: the reference's polarity).
+                sizes = gs.sizes
+                if int(sizes.max()) > max_num_nodes:   # the reference fails here with a shape error (:106)
+                    raise ValueError(f"the masked encoder needs every graph within max_input_len = {max_len} nodes "
+                                     f"(largest graph of the batch: {int(sizes.max())})")
+                keep_bits = ops.adjacency_bits(gs, max_num_nodes, key_valid=src_padding_mask, self_loops=self.adj_self_loops)
+                transformer_out = self.masked_transformer_encoder(transformer_out.transpose(0, 1), attn_mask=keep_bits).transpose(0, 1)
             if self.num_encoder_layers > 0:
                 transformer_out, _ = enc(transformer_out, src_padding_mask)
             transformer_out = transformer_out.float()

@@ -6,7 +6,8 @@ The reference materialises (B, nh, T, T) scores, fills them where the dense `att
 the per-key `valid_input_mask` (B,T) is 0 with the finite value -1e6 and soft-maxes; here q, k, v
 are projected by the HIP linear kernel into one (B*T, 3C) buffer and gt_attn_fwd/bwd applies the
 same masked_fill semantics in-register (a fully masked row becomes uniform, filled scores carry no
-gradient).  No shipped reference config enables this encoder (`num_encoder_layers_masked`
+gradient).  `attn_mask` may also be an `ops.AdjacencyBits` (one keep-bit per score, the key mask folded in:
+`ops.adjacency_bits`), which every module here hands down unchanged.  No shipped reference config enables this encoder (`num_encoder_layers_masked`
 defaults to 0, :108); `transformer_prenorm` is not forwarded by the reference (:114-121), so the
 blocks are always pre-norm here too.
 """
@@ -40,16 +41,19 @@ class CausalSelfAttention(nn.Module):
         self.n_head = n_head
 
     def forward(self, x, attn_mask: torch.Tensor = None, valid_input_mask: torch.Tensor = None, mask_value=-1e6):
-        """x (B,T,C) batch-first; attn_mask (B,T,T): 0 = fill; valid_input_mask (B,T): 0 = fill that key."""
+        """x (B,T,C) batch-first; attn_mask (B,T,T): 0 = fill; valid_input_mask (B,T): 0 = fill that key.
+        attn_mask may be an ops.AdjacencyBits instead (the same predicate as bits, built by ops.adjacency_bits with the
+        valid_input_mask already folded in: pass no valid_input_mask beside it)."""
         B, T, C = x.size()
+        bits = attn_mask if isinstance(attn_mask, ops.AdjacencyBits) else None
         rows = x.reshape(B * T, C)
         qkv = torch.cat([ops.linear_module(self.query, rows), ops.linear_module(self.key, rows),
                          ops.linear_module(self.value, rows)], dim=1)
         p = self.attn_drop.p if self.training else 0.0
         seed = int(torch.empty((), dtype=torch.int64).random_().item()) if p > 0 else 0
         y = ops.attention(qkv, _BatchLayout(B, T, x.device), self.n_head, dropout_p=p, seed=seed,
-                          scale=1.0 / math.sqrt(C // self.n_head), dense_mask=attn_mask, key_valid=valid_input_mask,
-                          mask_value=mask_value)
+                          scale=1.0 / math.sqrt(C // self.n_head), dense_mask=None if bits is not None else attn_mask,
+                          key_valid=valid_input_mask, mask_value=mask_value, keep_bits=bits)
         return ops.dropout(ops.linear_module(self.proj, y), self.resid_drop.p, self.training).view(B, T, C)   # resid_drop (:54)
 
 

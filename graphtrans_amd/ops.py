@@ -359,50 +359,105 @@ def seq_scatter(tokens, base, gs, lay):
 # ------------------------------------------------------------------------------------------------
 # fused attention
 # ------------------------------------------------------------------------------------------------
+class AdjacencyBits:
+    """The masked encoder's attention mask as keep-bits (gt_adj_mask_bits): `bits` (B, T, W) int32 holding uint32 words, W = ceil(T / 32);
+    key k of query q is bit k & 31 of word k >> 5 of row q, 1 = keep, 0 = the score is filled.  A key_valid mask is already folded in."""
+
+    __slots__ = ("bits", "B", "T", "W")
+
+    def __init__(self, bits, B, T):
+        self.bits, self.B, self.T, self.W = bits, int(B), int(T), (int(T) + 31) // 32
+        if bits.dtype != torch.int32 or tuple(bits.shape) != (self.B, self.T, self.W):
+            raise ValueError(f"keep-bits must be int32 of shape {(self.B, self.T, self.W)}, got {bits.dtype} {tuple(bits.shape)}")
+
+    def dense(self):
+        """float (B, T, T), 1.0 = keep: the dense_mask form of the same predicate (torch ops; tests and debugging only)"""
+        shifts = torch.arange(32, dtype=torch.int32, device=self.bits.device)
+        on = (self.bits.unsqueeze(-1) >> shifts) & 1   # (arithmetic shift of the int32 container: bit j still lands in bit 0)
+        return on.reshape(self.B, self.T, self.W * 32)[:, :, :self.T].float()
+
+
+def adjacency_bits(gs, T, key_valid=None, self_loops=True):
+    """AdjacencyBits of a batch from its GraphStructure: bit (b, q, k) = q, k < n_b and (edge (ptr_b + q) -> (ptr_b + k), or self_loops
+    and q == k) and key_valid[b][k] != 0 -- make_adj_list (data/adj_list.py) placed top-left (models/gnn_transformer.py:104-107), with
+    CausalSelfAttention's valid_input_mask fill folded in.  key_valid: (B, T), any dtype, optional.  A graph with more than T nodes
+    is cut to its first T: callers that follow the reference reject such a batch before they come here."""
+    T = int(T)
+    if T <= 0:
+        raise ValueError("adjacency_bits: T must be positive")
+    if torch.device(gs.device).type != "cuda":
+        raise RuntimeError("adjacency_bits runs on the GPU only (no CPU fallback)")
+    kv = None
+    if key_valid is not None:
+        if tuple(key_valid.shape) != (gs.B, T):
+            raise ValueError(f"key_valid must be {(gs.B, T)}, got {tuple(key_valid.shape)}")
+        kv = _dev(key_valid.float(), "key_valid")
+    bits = torch.empty((gs.B, T, (T + 31) // 32), dtype=torch.int32, device=gs.device)
+    _lib.launch("gt_adj_mask_bits", _ptr(gs.graph_ptr), _ptr(gs.out_ptr), _ptr(gs.out_dst), gs.N, gs.E, gs.B, T, _ptr(kv),
+                1 if self_loops else 0, _ptr(bits), _stream())
+    return AdjacencyBits(bits, gs.B, T)
+
+
 class _Attention(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, qkv, lay, nhead, scale, dropout_p, seed, dense_mask=None, key_valid=None, mask_value=0.0):
+    def forward(ctx, qkv, lay, nhead, scale, dropout_p, seed, dense_mask=None, key_valid=None, mask_value=0.0, keep_bits=None):
         qkv = _dev(qkv, "qkv")
         dense_mask = None if dense_mask is None else _dev(dense_mask.float(), "attn_mask")
         key_valid = None if key_valid is None else _dev(key_valid.float(), "valid_input_mask")
+        bits = None if keep_bits is None else _dev(keep_bits.bits, "keep_bits")
         rows, d3 = qkv.shape
         d = d3 // 3
         alloc = torch.empty if getattr(lay, "exact", True) else torch.zeros   # device-built layout: rows past the true count stay 0
         out = alloc((rows, d), dtype=qkv.dtype, device=qkv.device)
         lse = torch.empty((2, nhead, rows), dtype=torch.float32, device=qkv.device)
         meta = dict(lay=lay, d=d, nhead=nhead, elt=qkv.element_size())
-        _lib.launch("gt_attn_fwd", _dtype_code(qkv), _ptr(qkv), _ptr(out), _ptr(lse), rows, d, nhead, _ptr(lay.desc),
-                    lay.B, lay.row_stride, lay.max_npos, _ptr(getattr(lay, "work", None)), getattr(lay, "num_work", 0),
-                    _ptr(dense_mask), _ptr(key_valid), float(mask_value), scale, dropout_p, seed, _stream(), meta=meta)
+        head = (_dtype_code(qkv), _ptr(qkv), _ptr(out), _ptr(lse), rows, d, nhead, _ptr(lay.desc), lay.B, lay.row_stride, lay.max_npos,
+                _ptr(getattr(lay, "work", None)), getattr(lay, "num_work", 0))
+        if bits is not None:
+            _lib.launch("gt_attn_fwd_bits", *head, _ptr(bits), keep_bits.T, float(mask_value), scale, dropout_p, seed, _stream(), meta=meta)
+        else:
+            _lib.launch("gt_attn_fwd", *head, _ptr(dense_mask), _ptr(key_valid), float(mask_value), scale, dropout_p, seed, _stream(),
+                        meta=meta)
         ctx.meta = meta
-        ctx.save_for_backward(qkv, out, lse, dense_mask, key_valid)
-        ctx.cfg = (lay, nhead, scale, dropout_p, seed, mask_value)
+        ctx.save_for_backward(qkv, out, lse, dense_mask, key_valid, bits)
+        ctx.cfg = (lay, nhead, scale, dropout_p, seed, mask_value, None if keep_bits is None else keep_bits.T)
         return out
 
     @staticmethod
     def backward(ctx, g):
-        qkv, out, lse, dense_mask, key_valid = ctx.saved_tensors
-        lay, nhead, scale, dropout_p, seed, mask_value = ctx.cfg
+        qkv, out, lse, dense_mask, key_valid, bits = ctx.saved_tensors
+        lay, nhead, scale, dropout_p, seed, mask_value, bits_T = ctx.cfg
         g = _dev(g.to(qkv.dtype), "grad")
         rows, d3 = qkv.shape
         # rows that belong to no sequence position do not exist in either layout -> fully written
         dqkv = torch.empty_like(qkv) if getattr(lay, "exact", True) else torch.zeros_like(qkv)
         delta = torch.empty((nhead, rows), dtype=torch.float32, device=qkv.device)
-        _lib.launch("gt_attn_bwd", _dtype_code(qkv), _ptr(qkv), _ptr(out), _ptr(g), _ptr(lse), _ptr(delta),
-                    _ptr(dqkv), rows, d3 // 3, nhead, _ptr(lay.desc), lay.B, lay.row_stride, lay.max_npos,
-                    _ptr(getattr(lay, "work", None)), getattr(lay, "num_work", 0), _ptr(dense_mask), _ptr(key_valid),
-                    float(mask_value), scale, dropout_p, seed, _stream(), meta=ctx.meta)
-        return dqkv, None, None, None, None, None, None, None, None
+        head = (_dtype_code(qkv), _ptr(qkv), _ptr(out), _ptr(g), _ptr(lse), _ptr(delta), _ptr(dqkv), rows, d3 // 3, nhead, _ptr(lay.desc),
+                lay.B, lay.row_stride, lay.max_npos, _ptr(getattr(lay, "work", None)), getattr(lay, "num_work", 0))
+        if bits is not None:
+            _lib.launch("gt_attn_bwd_bits", *head, _ptr(bits), bits_T, float(mask_value), scale, dropout_p, seed, _stream(), meta=ctx.meta)
+        else:
+            _lib.launch("gt_attn_bwd", *head, _ptr(dense_mask), _ptr(key_valid), float(mask_value), scale, dropout_p, seed, _stream(),
+                        meta=ctx.meta)
+        return dqkv, None, None, None, None, None, None, None, None, None
 
 
-def attention(qkv, lay, nhead, dropout_p=0.0, seed=0, scale=None, dense_mask=None, key_valid=None, mask_value=-1e6):
+def attention(qkv, lay, nhead, dropout_p=0.0, seed=0, scale=None, dense_mask=None, key_valid=None, mask_value=-1e6, keep_bits=None):
     """ctx rows = softmax(mask(scale q k^T)) v per (sequence, head); qkv (rows, 3*d_model).
-    dense_mask (B,T,T) / key_valid (B,T): CausalSelfAttention's masked_fill(mask == 0, mask_value)."""
+    dense_mask (B,T,T) / key_valid (B,T): CausalSelfAttention's masked_fill(mask == 0, mask_value).
+    keep_bits: an AdjacencyBits holding the same predicate as bits (key_valid folded in); exclusive with the two dense masks."""
     d = qkv.shape[1] // 3
     if scale is None:
         scale = float(d // nhead) ** -0.5
+    if keep_bits is not None:
+        if dense_mask is not None or key_valid is not None:
+            raise ValueError("attention: keep_bits already holds the whole mask; pass it without dense_mask / key_valid")
+        if not isinstance(keep_bits, AdjacencyBits):
+            raise TypeError("attention: keep_bits must be an AdjacencyBits (ops.adjacency_bits)")
+        if keep_bits.B != lay.B:
+            raise ValueError(f"attention: keep_bits holds {keep_bits.B} sequences, the layout {lay.B}")
     return _Attention.apply(qkv, lay, nhead, float(scale), float(dropout_p), int(seed), dense_mask, key_valid,
-                            float(mask_value))
+                            float(mask_value), keep_bits)
 
 
 # ------------------------------------------------------------------------------------------------

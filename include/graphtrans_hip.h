@@ -186,6 +186,18 @@ int gt_graph_prep(const int64_t* edge_index, const int64_t* batch, int64_t num_n
                   int32_t* in_eid,
                   int32_t* out_ptr, int32_t* out_dst, int32_t* out_eid, float* deg, float* dis,
                   int32_t* status, void* workspace, size_t workspace_bytes, gt_stream_t stream);
+/* The attention mask of the masked encoder as keep-bits, from the structure above.  Replaces the host-side make_adj_list
+ * (data/adj_list.py: a dense (n, n) array per graph, pickled) and its top-left placement into a (B, T, T) fp32 tensor
+ * (models/gnn_transformer.py:104-107).
+ *   bits [B][T][W] uint32, W = ceil(T / 32); key k of query q = bit k & 31 of word k >> 5 of row q (= bit k & 7 of byte k >> 3).
+ *   With n_b = graph_ptr[b+1] - graph_ptr[b], bit (b, q, k) is 1 exactly when q < n_b, k < n_b, the batch has an edge
+ *   (graph_ptr[b] + q) -> (graph_ptr[b] + k) (source = edge_index row 0; duplicates are harmless) or self_loops != 0 and q == k
+ *   (the reference's np.eye), and key_valid[b][k] != 0 when key_valid ([B][T] fp32, optional) is given.  Rows q >= n_b and the bits
+ *   k >= T of the last word are 0.  Every word of bits is written; a graph with n_b > T is cut to its first T nodes (callers that
+ *   follow the reference reject such a batch).  T <= 32768, else GT_ERR_UNSUPPORTED.  No atomics: the result is deterministic. */
+int gt_adj_mask_bits(const int32_t* graph_ptr, const int32_t* out_ptr, const int32_t* out_dst, int64_t num_nodes,
+                     int64_t num_edges, int64_t num_graphs, int64_t T, const float* key_valid, int self_loops,
+                     uint32_t* bits, gt_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------------
  * Fused message + aggregate + update of GCNConv / GINConv.
@@ -457,6 +469,20 @@ int gt_attn_bwd(int dtype, const void* qkv, const void* ctx, const void* d_ctx, 
                 int64_t num_seqs, int64_t row_stride, int64_t max_npos, const int32_t* work_items, int64_t num_work,
                 const float* dense_mask, const float* key_valid, float mask_value, float scale, float dropout_p,
                 uint64_t seed, gt_stream_t stream);
+/* The same masked_fill attention with the predicate as BITS (gt_adj_mask_bits below, or any producer of that layout):
+ * keep_bits [num_seqs][bits_T][ceil(bits_T / 32)] uint32, key k of query q = bit k & 31 of word k >> 5 of row q, 1 = keep, 0 = the
+ * score is filled with mask_value; a key_valid mask is folded into the bits by their producer.  Rows are pitched by bits_T, so the
+ * sequences may differ in npos; max_npos > bits_T is GT_ERR_UNSUPPORTED.  Everything else (mask_value, dropout, lse, work_items) as
+ * in gt_attn_fwd / gt_attn_bwd with dense masks, and the same kernels: results are bit-identical to the dense form of the same mask. */
+int gt_attn_fwd_bits(int dtype, const void* qkv, void* ctx, float* lse, int64_t total_rows, int64_t d_model, int nhead,
+                     const int32_t* seq_desc, int64_t num_seqs, int64_t row_stride, int64_t max_npos,
+                     const int32_t* work_items, int64_t num_work, const uint32_t* keep_bits, int64_t bits_T,
+                     float mask_value, float scale, float dropout_p, uint64_t seed, gt_stream_t stream);
+int gt_attn_bwd_bits(int dtype, const void* qkv, const void* ctx, const void* d_ctx, const float* lse, float* delta,
+                     void* d_qkv, int64_t total_rows, int64_t d_model, int nhead, const int32_t* seq_desc,
+                     int64_t num_seqs, int64_t row_stride, int64_t max_npos, const int32_t* work_items, int64_t num_work,
+                     const uint32_t* keep_bits, int64_t bits_T, float mask_value, float scale, float dropout_p,
+                     uint64_t seed, gt_stream_t stream);
 /* Pooled mode: after the LAST encoder layer only one row per sequence is read (cls / last pooling, models/gnn_transformer.py:113-114):
  * gt_attn_fwd_last computes the 64-row tile that holds the LAST position of every sequence only (ctx / lse rows outside those tiles
  * are not written); gt_attn_bwd_last is its backward for a d_ctx that is non-zero in those last positions only: dQ for the last
