@@ -7,6 +7,11 @@ of interpreter time per step).  Now the sequencing lives behind `gt_model_forwar
 pointers, sizes, gradient offsets, streams, events) and one `gt_model_batch` per step, allocates the two arenas the driver asks for,
 and hands the flat gradient buffer's slices to the parameters.  Autograd sees a single node.
 
+A model's plan is built in three steps.  (1) model_layout.py, host only: `ModelLayout(model)` reads the module tree and lays out the
+flat gradient buffer, the non-pointer fields of `gt_model` and of the layer descriptors, the storage groups and the list of pointers
+to write; `structural_ok` is the half of `eligible` that asks the same tree.  (2) `bind_storage` here, device-agnostic: re-homes the
+storage groups, then writes every pointer.  (3) `_Plan` here: streams, events, PNA and weight images, the flat buffer.
+
 Covered configuration (everything else keeps using the module path, see `eligible`):
   GNN_node / GNN_node_Virtualnode with GCNConv or GINConv layers, Linear(<=4, D), BondEncoder-style
   embedding tables or "zero" edge encoders,
@@ -37,9 +42,11 @@ import weakref
 import numpy as np
 import torch
 
-from . import _lib, layers
+from . import _lib
 from ._lib import GT_BF16, GT_EDGE_LINEAR, GT_EDGE_NONE, GT_EDGE_TABLES, GT_F32
 from .graph import StageRingDesc, _stream, stage_ring
+from .model_layout import (MAXL, MAXT, W_MAX_BOUND, ModelLayout, _frozen_ok, edge_encoder, emb_dim, frozen_pattern, head_kind,  # noqa: F401
+                           input_encoder, model_parts, readout_kind, structural_ok)   # (callers and tests read them as engine.<name>)
 
 
 OVERLAP_VN = os.environ.get("GT_OVERLAP_VN", "1") != "0"
@@ -51,41 +58,7 @@ PREP_OVERLAP = os.environ.get("GT_PREP_OVERLAP", "1") != "0"
 DW_OVERLAP_MIN_ELEMS = 1 << 20   # nodes x emb_dim of the batch
 VN_DEFER_DW = os.environ.get("GT_VN_DEFER_DW", "1") != "0"
 
-MAXL, MAXT = 16, 16   # GT_MODEL_MAX_LAYERS, GT_MODEL_MAX_TABLES
 _vp, _i32, _i64, _f32 = C.c_void_p, C.c_int32, C.c_int64, C.c_float
-
-
-def _c4(n):
-    return (n + 3) // 4 * 4
-
-
-def readout_kind(model):
-    """GT_POOL_* of a `models.gnn.GNN` or a `models.pna.PNANet` (the driver's read-out mode: message passing -> per-graph pooling ->
-    heads), 0 for the token-path models"""
-    from .models.gnn import GNN
-    from .models.pna import PNANet
-    from .ops import POOL_KINDS
-    return POOL_KINDS[model.graph_pooling] if isinstance(model, (GNN, PNANet)) else 0
-
-
-def model_parts(model):
-    """(message-passing stack, token encoder, input encoder) of a model -- THE place that knows where each model family keeps them:
-    `gnn_node` / `transformer_encoder` / `gnn_node.node_encoder` for the four families with message passing (no token encoder in the
-    read-out mode), None / `transformer` / `node_encoder` for `models.transformer.Transformer`, which has no message passing (the
-    driver's encoder-only mode, gt_model::enc_only)."""
-    from .models.transformer import Transformer
-    if isinstance(model, Transformer):
-        return None, model.transformer, model.node_encoder
-    gnn = model.gnn_node
-    return gnn, (None if readout_kind(model) else model.transformer_encoder), gnn.node_encoder
-
-
-def head_kind(model):
-    """gt_model::head_kind: 0 the linear heads, 1 the narrow MLP of `PNANet` (max_seq_len None), 2 its per-position two-layer heads"""
-    from .models.pna import PNANet
-    if not isinstance(model, PNANet):
-        return 0
-    return 1 if model.max_seq_len is None else 2
 
 
 # ---- mirrors of the driver's structs (include/graphtrans_hip.h; sizes checked against gt_model_abi_sizes at first use) ----------
@@ -170,10 +143,6 @@ def _side_stream(device, which):
     return st
 
 
-def _arr(ctype, vals):
-    return (ctype * max(len(vals), 1))(*vals)
-
-
 def _image_set(imgs):
     """gt_image_set view of a w3.W3Images / W1Images object (its ctypes arrays stay owned by `imgs`)"""
     s = ImageSet()
@@ -199,166 +168,44 @@ def _rehome(params):
     return flat, offs
 
 
-def _bn_fields(desc, bn, name="bn", hyper=False):
-    """a descriptor's BatchNorm fields from the module: the running buffers `<name>_rm / _rv / _nbt`; hyper: this is the module
-    whose momentum and eps the descriptor's ONE bn_momentum / bn_eps pair carries"""
-    setattr(desc, name + "_rm", bn.running_mean.data_ptr())
-    setattr(desc, name + "_rv", bn.running_var.data_ptr())
-    setattr(desc, name + "_nbt", bn.num_batches_tracked.data_ptr())
-    if hyper:
-        desc.bn_momentum, desc.bn_eps = float(bn.momentum), float(bn.eps)
-
-
 PNA_TOWER_IMAGES = os.environ.get("GT_PNA_TOWER_IMAGES", "1") != "0"   # bf16x3 images of the PNA tower weights (grouped k_lin3)
-W_MAX_BOUND = 64   # W3_MAX_BOUND / W1_MAX_BOUND of the library's bind tables
 
 
 # ---------------------------------------------------------------------------------------------------
-# plan: parameter order, gradient layout, the driver's model struct (built once per model)
+# plan: a model's layout (model_layout.ModelLayout, host only) bound to its storage and to a device, built once per model
 # ---------------------------------------------------------------------------------------------------
-class _Plan:
+def bind_storage(lay, cm):
+    """Step 2 of a plan, device-agnostic (`_rehome` and `data_ptr()` work on CPU tensors): the parameters of every storage group of
+    the layout become views of one matrix, then every parameter and buffer pointer goes into `cm` and the layout's descriptors.
+    ORDER: re-homing gives a parameter new storage, so a pointer read before its group is re-homed points at freed memory.  Every
+    group is re-homed HERE, in this one loop, and no code reads a data_ptr() before it has run."""
+    for group in lay.storage_groups:
+        _rehome(group)
+    lay.fill(cm)
+    for desc, name, t in lay.ptrs:
+        setattr(cm if desc is None else desc, name, t.data_ptr())
+    for t, w in enumerate(lay.embed):
+        cm.tables[t] = w.data_ptr()
+    cm.conv_layers = C.cast(lay.conv_desc, _vp) if lay.conv_desc is not None else None
+    cm.vn = C.cast(lay.vn_desc, _vp) if (lay.has_vn and lay.L > 1) else None
+    cm.enc = C.cast(lay.enc_desc, _vp) if lay.enc_layers else None
+
+
+class _Plan(ModelLayout):
+    """A layout IS the plan's base class: everything the per-step path reads stays a plain attribute of the plan object."""
     def __init__(self, model):
-        from .modules.conv import GINConv
-        from .modules.gnn_module import GNN_node_Virtualnode
         from . import w3
         _check_abi()
         lib = _lib.lib()
-        self.readout = readout_kind(model)
-        gnn, enc, ne = model_parts(model)   # (read-out mode: nothing behind gnn_node but the heads; encoder-only mode: no gnn_node)
-        self.enc_only = gnn is None
-        self.L, self.has_vn = (0 if gnn is None else gnn.num_layer), isinstance(gnn, GNN_node_Virtualnode)
-        if gnn is None:   # models.transformer.Transformer: the node rows are the token rows
-            self.kind = "gcn"   # (gt_model::conv is not read without conv layers)
-            self.D = enc.d_model
-            self.jk_cat = False
-        elif hasattr(gnn, "layers"):   # PNANodeEmbedding
-            self.kind = "pna"
-            self.D = gnn.layers[0].in_channels
-            self.jk_cat = False
-        else:
-            self.kind = "gin" if isinstance(gnn.convs[0], GINConv) else "gcn"
-            self.D = gnn.convs[0].emb_dim
-            self.jk_cat = gnn.JK == "cat"
-        self.d = self.D if self.readout else enc.d_model   # the heads' input width
-        self.dev = next(model.parameters()).device
-        self.total = 0
-        self.params = []   # (param, offset)
-        self._cache = {}   # per batch size: small index arrays
-        self._keep = []    # ctypes arrays / tensors the struct points into
-        L, D, d = self.L, self.D, self.d
-
-        def seg(p):
-            off = self.total
-            self.params.append((p, off))
-            self.total += _c4(p.numel())
-            return off
-
-        def block(ps):
-            """lay out a block of parameters one behind the other: the block's first offset"""
-            return [seg(p) for p in ps][0]
-
+        super().__init__(model)   # step 1: the layout (host only)
         cm = self.cm = ModelDesc()
-        cm.enc_only = int(self.enc_only)
-        if hasattr(ne, "type_encoder"):  # ASTNodeEncoder
-            self.embed = [ne.type_encoder.weight, ne.attribute_encoder.weight, ne.depth_encoder.weight]
-            self.embed_clamp = [-1, -1, int(ne.max_depth)]
-            self.embed_kind = "ast"
-        elif type(ne) is torch.nn.Linear:   # TU datasets / the ER stress: dense float features (dataset/tud.py:65)
-            self.embed, self.embed_clamp, self.embed_kind = [], [], "linear"
-            self.ne_lin = ne
-            self.ne_K = int(ne.in_features)
-        else:
-            self.embed = [e.weight for e in ne.atom_embedding_list]
-            self.embed_clamp = [-1] * len(self.embed)
-            self.embed_kind = "atom"
-        cm.embed_kind = {"atom": 0, "linear": 1, "ast": 2}[self.embed_kind]
-        cm.n_tables = len(self.embed)
-        for t, w in enumerate(self.embed):
-            cm.off_tables[t] = seg(w)
-        cm.off_ne_w = cm.off_ne_b = -1
-        if self.embed_kind == "linear":
-            cm.off_ne_w, cm.off_ne_b = seg(ne.weight), seg(ne.bias)
-            cm.ne_K = self.ne_K
-        self.vn_emb = gnn.virtualnode_embedding.weight if self.has_vn else None
-        cm.off_vn_emb = seg(self.vn_emb) if self.has_vn else -1
-        self.w3_weights = []
-        self.etab_flat = None
-        self.conv_desc = None
-        if self.enc_only:
-            pass   # no conv descriptors, no virtual-node streams or events, no gnn2transformer
-        elif self.kind == "pna":
-            self._init_pna(gnn, block)
-        else:
-            self._init_convs(gnn, seg, block)
-        nvn = L - 1 if self.has_vn else 0
-        self.vn_desc = (layers.VnUpdateDesc * max(nvn, 1))()
-        if self.has_vn:
-            for l, seq in enumerate(gnn.mlp_virtualnode_list):
-                m = list(seq)
-                ps = [m[0].weight, m[0].bias, m[1].weight, m[1].bias, m[3].weight, m[3].bias, m[4].weight, m[4].bias]
-                cm.off_vn[l] = block(ps)
-                desc = self.vn_desc[l]
-                desc.D = D
-                for name, p in zip(("w1", "b1", "bn1_w", "bn1_b", "w2", "b2", "bn2_w", "bn2_b"), ps):
-                    setattr(desc, name, p.data_ptr())
-                _bn_fields(desc, m[1], "bn1", hyper=True)
-                _bn_fields(desc, m[4], "bn2")
-        for k in ("off_g2t_w", "off_g2t_b", "off_cls", "off_nin_w", "off_nin_b", "off_nout_w", "off_nout_b"):
-            setattr(cm, k, -1)
-        self.g2t = self.cls = self.norm_in = self.norm_out = None
-        self.enc_layers, self.w3_enc_weights = [], []
-        self.enc_desc = (layers.EncoderLayerDesc * 1)()
-        if not self.readout:
-            self._init_encoder(model, enc, seg, block)
-        # ---- the head block: hidden weights, hidden biases (PNANet only), output weights, output biases
-        self.head_kind = head_kind(model)
-        cm.head_kind = self.head_kind
-        cm.off_hid_w = cm.off_hid_b = cm.off_hid2_w = cm.off_hid2_b = -1
-        self.hid_flat = ()
-        if self.head_kind == 1:     # mlp = Linear(D, 35) -> ReLU -> Linear(35, 17) -> ReLU -> Linear(17, T)  (models/pna.py:53-60)
-            l1, l2, l3 = model.mlp[0], model.mlp[2], model.mlp[4]
-            cm.off_hid_w, cm.off_hid2_w, cm.off_hid_b, cm.off_hid2_b = seg(l1.weight), seg(l2.weight), seg(l1.bias), seg(l2.bias)
-            cm.head_h1, cm.head_h2 = l1.out_features, l2.out_features
-            cm.hid_w, cm.hid_b, cm.hid2_w, cm.hid2_b = (t.data_ptr() for t in (l1.weight, l1.bias, l2.weight, l2.bias))
-            self.heads = [l3]
-        elif self.head_kind == 2:   # per position Linear(D, D) -> ReLU -> Linear(D, T)  (models/pna.py:62-71): the hidden layers' storage
-            hid = [seq[0] for seq in model.graph_pred_linear_list]   # becomes the stacked [L*D][D] matrix, as the output layers' below
-            cm.head_pos = len(hid)
-            cm.off_hid_w = self.total
-            for h in hid:
-                self.params.append((h.weight, self.total))
-                self.total += h.weight.numel()
-            cm.off_hid_b = self.total
-            for h in hid:
-                self.params.append((h.bias, self.total))
-                self.total += h.bias.numel()
-            self.hid_flat = (_rehome([h.weight for h in hid])[0], _rehome([h.bias for h in hid])[0])
-            cm.hid_w, cm.hid_b = self.hid_flat[0].data_ptr(), self.hid_flat[1].data_ptr()
-            self.heads = [seq[2] for seq in model.graph_pred_linear_list]
-        elif model.max_seq_len is None:
-            self.heads = [model.graph_pred_linear]
-        else:
-            self.heads = list(model.graph_pred_linear_list)
-        self.num_tasks = model.num_tasks
-        self.Nh = sum(h.weight.shape[0] for h in self.heads)
-        self.ldy = _c4(self.Nh)
-        # head gradients: one [Nh][d] block and one [Nh] block; the per-head grads are slices of them
-        cm.off_head_w = self.total
-        for h in self.heads:
-            self.params.append((h.weight, self.total))
-            self.total += h.weight.numel()
-        self.total = _c4(self.total)
-        cm.off_head_b = self.total
-        for h in self.heads:
-            self.params.append((h.bias, self.total))
-            self.total += h.bias.numel()
-        self.total = _c4(self.total)
-        # the max_seq_len prediction heads (models/gnn_transformer.py:120-126) run as ONE GEMM over their stacked weights: the
-        # parameters' storage IS the stacked matrix -- each head's weight / bias becomes a view of it
-        self.head_w_flat, self.head_b_flat = self.heads[0].weight, self.heads[0].bias
-        if len(self.heads) > 1:
-            self.head_w_flat, self.head_b_flat = _rehome([h.weight for h in self.heads])[0], _rehome([h.bias for h in self.heads])[0]
-        cm.grad_total = self.total
+        bind_storage(self, cm)    # step 2: storage
+        # ---- step 3: device resources
+        self.dev = next(model.parameters()).device
+        self._cache = {}   # per batch size: small index arrays
+        self.pe_ptr = self.pe.data_ptr() if self.pe is not None else 0
+        cm.vn_defer_dw = int(VN_DEFER_DW)
+        tower_views = self._bind_pna_images() if self.kind == "pna" else []
         # persistent flat gradient buffer and its per-parameter views
         self.flat = torch.zeros(self.total, dtype=torch.float32, device=self.dev)
         self.views = [self.flat[o:o + p.numel()].view(p.shape) for p, o in self.params]
@@ -366,45 +213,8 @@ class _Plan:
         self.plist = [p for p, _ in self.params]
         self.param_ptrs = tuple(p.data_ptr() for p in self.plist)
         self.frozen = None   # set_frozen: which parameters the backward hands gradients to
-        # ---- the rest of the static struct
-        cm.conv = {"gcn": 0, "gin": 1, "pna": 2}[self.kind]
-        cm.L, cm.n_enc, cm.has_vn, cm.jk_cat = L, len(self.enc_layers), int(self.has_vn), int(self.jk_cat)
-        cm.residual = int(bool(gnn.residual)) if gnn is not None else 0
-        cm.D, cm.d, cm.Nh, cm.ldy = D, d, self.Nh, self.ldy
-        cm.readout = self.readout
-        cm.max_input_len = int(enc.max_input_len) if enc is not None else 0
-        cm.with_cls = int(self.cls is not None)
-        # PositionalEncoding (token_layout="packed" only, see GNNTransformer._use_packed): the module's buffer, read as [max_len][d]
-        pe = getattr(model, "pos_encoder", None)
-        self.pe = pe.pe if pe is not None else None
-        self.pe_ptr = self.pe.data_ptr() if pe is not None else 0
-        if pe is not None:
-            cm.pe, cm.pe_rows = self.pe_ptr, int(self.pe.shape[0])
-        cm.vn_defer_dw = int(VN_DEFER_DW)
-        cm.conv_layers = C.cast(self.conv_desc, _vp) if self.conv_desc is not None else None
-        cm.vn = C.cast(self.vn_desc, _vp) if nvn else None
-        cm.enc = C.cast(self.enc_desc, _vp) if self.enc_layers else None
-        for t, w in enumerate(self.embed):
-            cm.tables[t], cm.table_rows[t], cm.table_clamp[t] = w.data_ptr(), int(w.shape[0]), self.embed_clamp[t]
-        # x_0 = h_0 + vn_0[batch] with vn_0 = the ONE row of virtualnode_embedding for every graph (gnn_module.py:195):
-        # the embedding-sum kernel takes it as one more table whose index column is a stride-0 zero
-        self.vn0_in_embed = self.has_vn and self.embed_kind != "linear" and len(self.embed) < 16
-        cm.vn0_in_embed = int(self.vn0_in_embed)
-        self.embed_sorted = bool(self.embed) and max(int(t.shape[0]) for t in self.embed) <= 16384
-        cm.embed_sorted = int(self.embed_sorted)
         self.zero_i64 = torch.zeros(1, dtype=torch.int64, device=self.dev)
         cm.zero_i64 = self.zero_i64.data_ptr()
-        cm.vn_emb = self.vn_emb.data_ptr() if self.has_vn else None
-        if self.embed_kind == "linear":
-            cm.ne_w, cm.ne_b = ne.weight.data_ptr(), ne.bias.data_ptr()
-        if self.g2t is not None:
-            cm.g2t_w, cm.g2t_b = self.g2t.weight.data_ptr(), self.g2t.bias.data_ptr()
-        cm.cls = self.cls.data_ptr() if self.cls is not None else None
-        if self.norm_in is not None:
-            cm.nin_w, cm.nin_b, cm.nin_eps = self.norm_in.weight.data_ptr(), self.norm_in.bias.data_ptr(), float(self.norm_in.eps)
-        if self.norm_out is not None:
-            cm.nout_w, cm.nout_b, cm.nout_eps = self.norm_out.weight.data_ptr(), self.norm_out.bias.data_ptr(), float(self.norm_out.eps)
-        cm.head_w, cm.head_b = self.head_w_flat.data_ptr(), self.head_b_flat.data_ptr()
         # streams: the virtual-node update of layer l only feeds layer l+1 (second stream beside layer l's conv / BatchNorm +
         # aggregate backward); the weight-gradient GEMMs run on a third stream beside the dX chain; the graph structure on a fourth
         self.side = _side_stream(self.dev, "vn") if (self.has_vn and OVERLAP_VN) else None
@@ -418,7 +228,7 @@ class _Plan:
             self._events.append(e)
             return e
         with torch.cuda.device(self.dev):
-            for l in range(L):
+            for l in range(self.L):
                 cm.ev_x[l], cm.ev_vn[l], cm.ev_dvn[l], cm.ev_extra[l], cm.ev_pool[l] = ev(), ev(), ev(), ev(), ev()
             cm.ev_vnemb, cm.ev_prep_begin, cm.ev_graph, cm.ev_w1 = ev(), ev(), ev(), ev()
             cm.ev_sort[0], cm.ev_sort[1], cm.ev_wt[0], cm.ev_wt[1] = ev(), ev(), ev(), ev()
@@ -426,8 +236,7 @@ class _Plan:
         # ---- weight images: bf16x3 (fp32-accurate big-M GEMMs on the bf16 pipe, csrc/linear3x.h) and fragment-order bf16 (encoder
         # layers, csrc/linear1.h); rebuilt by the driver at every forward (the optimizer changed the weights: one launch each), bound
         # per host thread inside the driver.  A weight list beyond the bind tables' 64 entries keeps the exact / tiled kernels.
-        if self.embed_kind == "linear" and _c4(self.ne_K) == self.ne_K:
-            self.w3_weights.append(self.ne_lin.weight)
+        self.w3_weights = self.w3_weights + tower_views + self.w3_tail
         self.imgs3 = self.imgs3e = self.imgs1 = None
         if w3.ENABLED:
             if self.w3_weights and len(self.w3_weights) <= W_MAX_BOUND:   # (none: the encoder-only mode with a table or a re-pitched encoder)
@@ -445,219 +254,40 @@ class _Plan:
         # range 0 -- what stage 1 of the backward completes -- holds every parameter outside gnn_node and nothing else
         # (encoder-only mode: what lies below the tail is the input encoder, and there is no frozen pattern)
         tail = self.ranges[0][0]
+        gnn, _, ne = model_parts(model)
         gnn_ids = {id(p) for p in (gnn if gnn is not None else ne).parameters()}
         self.gnn_plist = [p for p, o in self.params if o < tail]
         self.tail_outside_gnn = {id(p) for p in self.gnn_plist} == gnn_ids
         self.set_frozen(gnn is not None and frozen_pattern(model) == "gnn")
 
-    def _init_encoder(self, model, enc, seg, block):
-        """gnn2transformer (not in the encoder-only mode), cls / norm_input, the encoder layers and the final norm: gradient offsets and
-        descriptors (token path, encoder-only mode)"""
-        cm, d = self.cm, self.d
-        if not self.enc_only:
-            g2t = self.g2t = model.gnn2transformer
-            cm.off_g2t_w, cm.off_g2t_b = seg(g2t.weight), seg(g2t.bias)
-            self.w3_weights.append(g2t.weight)
-        self.cls = enc.cls_embedding
-        cm.off_cls = seg(self.cls) if self.cls is not None else -1
-        self.norm_in = enc.norm_input
-        cm.off_nin_w, cm.off_nin_b = (seg(enc.norm_input.weight), seg(enc.norm_input.bias)) if enc.norm_input is not None else (-1, -1)
-        self.enc_layers = list(enc.transformer.layers)
-        self.enc_desc = (layers.EncoderLayerDesc * max(len(self.enc_layers), 1))()
-        self.w3_enc_weights = []   # the encoder layers' GEMMs run in fp32 only in the fp32 mode (fp32 token rows)
-        for i, mod in enumerate(self.enc_layers):
-            ps = layers.encoder_layer_params(mod)
-            cm.off_enc[i] = block(ps)
-            desc = self.enc_desc[i]
-            desc.d_model, desc.ffn, desc.nhead = d, mod.linear1.weight.shape[0], enc.nhead
-            for name, p in zip(("in_w", "in_b", "out_w", "out_b", "l1_w", "l1_b", "l2_w", "l2_b", "n1_w", "n1_b", "n2_w", "n2_b"), ps):
-                setattr(desc, name, p.data_ptr())
-            desc.ln_eps = float(mod.norm1.eps)
-            desc.act = layers.ENC_ACT[enc.activation]
-            self.w3_enc_weights += [mod.self_attn.in_proj_weight, mod.self_attn.out_proj.weight, mod.linear1.weight, mod.linear2.weight]
-        self.norm_out = enc.transformer.norm
-        cm.off_nout_w, cm.off_nout_b = (seg(self.norm_out.weight), seg(self.norm_out.bias)) if self.norm_out is not None else (-1, -1)
-
-    def _init_convs(self, gnn, seg, block):
-        from .modules.conv import GINConv
-        cm, L, D = self.cm, self.L, self.D
-        # ---- conv layers.  Gradient block order of gt_gcn_layer_bwd: lin_w, lin_b, root, edge_w, edge_b, bn_w, bn_b;
-        # of gt_gin_layer_bwd: eps (20-float slot), edge tables | edge_w, edge_b, w1, b1, bn1_w, bn1_b, w2, b2, bn_w, bn_b
-        self.convs = list(zip(gnn.convs, gnn.batch_norms))
-        # BondEncoder-style tables: the aggregate kernels read ONE [rows][D] matrix per layer.  Instead of stacking a layer's tables
-        # by a torch.cat per step, the parameters' storage IS the stacked matrix -- each table's weight becomes a view of it (same
-        # Parameter objects, same state_dict keys; optim.FusedAdamW notices the move and rebuilds its tables)
-        self.etab_flat = None
-        tabs_all = [[t.weight for t in getattr(conv.edge_encoder, "bond_embedding_list", [])] for conv, _ in self.convs]
-        if any(tabs_all):
-            self.etab_flat = _rehome([t for tl in tabs_all for t in tl])[0]
-        self.conv_desc = ((layers.GinLayerDesc if self.kind == "gin" else layers.GcnLayerDesc) * L)()
-        for l, (conv, bn) in enumerate(self.convs):
-            desc = self.conv_desc[l]
-            ee = conv.edge_encoder
-            tabs = tabs_all[l]
-            if tabs:
-                edge, mode = tabs, "tables"
-            elif isinstance(ee, torch.nn.Module):
-                edge, mode = [ee.weight, ee.bias], "linear"
-            else:
-                edge, mode = [], None
-            if self.kind == "gcn":
-                plist = [conv.linear.weight, conv.linear.bias, conv.root_emb.weight, *edge, bn.weight, bn.bias]
-                self.w3_weights.append(conv.linear.weight)
-            else:
-                m = list(conv.mlp)
-                plist = [conv.eps, *edge, m[0].weight, m[0].bias, m[1].weight, m[1].bias, m[3].weight, m[3].bias, bn.weight, bn.bias]
-                self.w3_weights += [m[0].weight, m[3].weight]
-            if self.kind == "gin":
-                cm.off_conv[l] = seg(plist.pop(0))
-                self.total = cm.off_conv[l] + 20   # d_eps + the aggregate backward's scratch (GIN_EPS_SLOT in layers.hip)
-                block(plist)
-            else:
-                cm.off_conv[l] = block(plist)
-            desc.D = D
-            if self.kind == "gcn":
-                desc.lin_w, desc.lin_b, desc.root = conv.linear.weight.data_ptr(), conv.linear.bias.data_ptr(), conv.root_emb.weight.data_ptr()
-            else:
-                desc.eps = conv.eps.data_ptr()
-                desc.w1, desc.b1, desc.bn1_w, desc.bn1_b = m[0].weight.data_ptr(), m[0].bias.data_ptr(), m[1].weight.data_ptr(), m[1].bias.data_ptr()
-                desc.w2, desc.b2 = m[3].weight.data_ptr(), m[3].bias.data_ptr()
-                _bn_fields(desc, m[1], "bn1")
-            if mode == "linear":
-                desc.edge_mode = GT_EDGE_LINEAR
-                desc.edge_cols = ee.weight.shape[1]
-                desc.edge_w, desc.edge_b = ee.weight.data_ptr(), ee.bias.data_ptr()
-            elif mode == "tables":
-                desc.edge_mode = GT_EDGE_TABLES
-                desc.edge_cols, desc.table_rows = len(tabs), sum(int(t.shape[0]) for t in tabs)
-                acc = 0
-                for i, t in enumerate(tabs):
-                    desc.tab_off[i] = acc
-                    acc += int(t.shape[0])
-                desc.edge_w = tabs[0].data_ptr()   # the layer's stacked [rows][D] block
-            else:
-                desc.edge_mode = GT_EDGE_NONE
-            desc.bn_w, desc.bn_b = bn.weight.data_ptr(), bn.bias.data_ptr()
-            _bn_fields(desc, bn, hyper=True)
-
-    _SCALER_KIND = {None: 0, "identity": 0, "amplification": 1, "attenuation": 2, "linear": 3, "inverse_linear": 4}
-
-    def _init_pna(self, gnn, block):
-        """PNANodeEmbedding (modules/pna/pna_module.py:16-78): per layer lin / BatchNorm gradients in the layer block of the flat
-        buffer; the tower weights of ALL layers live in one flat storage (the parameters become views of it), from which the driver
-        rebuilds the re-stacked images [A ; B], [b | 0], the per-scaler post-Linear blocks and their bias with ONE gather per step."""
-        from .modules.pna.pna_module import _AGG_SLOT
-        cm, L, D = self.cm, self.L, self.D
-        convs = list(gnn.layers)
-        bns = [b.module for b in gnn.batch_norms]
-        self.convs = list(zip(convs, bns))
-        c0 = convs[0]
-        T, F = c0.towers, c0.F_in
-        A, S = len(c0.aggregators), len(c0._blocks)
-        first = S - len(c0.scalers)
-        cols = (A * len(c0.scalers) + 1) * F
-        K = c0.agg_slots          # the aggregate kernel's slot count: 4, or 6 with sum / var
-        KF = (1 + K) * F          # the post-Linear's operand [x | K aggregates] per tower
-        self.conv_desc = (layers.PnaLayerDesc * L)()
-        # ---- flat tower storage: per layer [pre_w (T,F,2F) | pre_b (T,F) | post_w (T,F,cols) | post_b (T,F)]
-        per_layer = T * F * 2 * F + T * F + T * F * cols + T * F
-        n_src = L * per_layer
-        towers = [p for conv in convs for nns in (conv.pre_nns, conv.post_nns)
-                  for p in [nn[0].weight for nn in nns] + [nn[0].bias for nn in nns]]
-        flat, offs = _rehome(towers)
-        assert flat.numel() == n_src and tuple(towers[0].shape) == (F, 2 * F) and tuple(towers[2 * T].shape) == (F, cols)
-        tower_params = list(zip(towers, offs))   # (param, offset inside the flat storage)
-        self.pna_flat = flat
-        # ---- image layout per layer: [pre_stack (T,2F,F) | pre_b2 (T,2F) | Wst (T,S*F,(1+K)F) | bst (T,S*F)] and the gather map
-        img_per_layer = T * 2 * F * F + T * 2 * F + T * S * F * KF + T * S * F
-        n_img = L * img_per_layer
-        mp = np.full(n_img, -1, dtype=np.int64)
-        t_ = np.arange(T).reshape(T, 1, 1)
+    def _bind_pna_images(self):
+        """the PNA tower images (model_layout.pna_maps) on the device, the descriptors' pointers into them, and -- where they fit
+        the bind table -- the views of the image buffer that get bf16x3 images too (returned)"""
+        cm, L, T, F, S, K = self.cm, self.L, self.pna_T, self.pna_F, self.pna_S, self.pna_K
+        self.pna_map = torch.from_numpy(self.pna_map_np.astype(np.int32)).to(self.dev)
+        self.pna_inv = torch.from_numpy(self.pna_inv_np.astype(np.int32)).to(self.dev)
+        self.pna_img = torch.zeros(self.pna_map_np.size, dtype=torch.float32, device=self.dev)
+        base = self.pna_img.data_ptr()
+        cm.pna_img, cm.pna_map, cm.pna_inv = base, self.pna_map.data_ptr(), self.pna_inv.data_ptr()
         for l in range(L):
-            sb = l * per_layer                      # source bases of this layer
-            s_pre_w, s_pre_b = sb, sb + T * F * 2 * F
-            s_post_w, s_post_b = s_pre_b + T * F, s_pre_b + T * F + T * F * cols
-            ib = l * img_per_layer
-            i_pre_w, i_pre_b = ib, ib + T * 2 * F * F
-            i_post_w, i_post_b = i_pre_b + T * 2 * F, i_pre_b + T * 2 * F + T * S * F * KF
-            r = np.arange(2 * F).reshape(1, 2 * F, 1)
-            k = np.arange(F).reshape(1, 1, F)
-            src = s_pre_w + t_ * (F * 2 * F) + np.where(r < F, r, r - F) * (2 * F) + np.where(r < F, 0, F) + k
-            mp[i_pre_w:i_pre_w + T * 2 * F * F] = src.reshape(-1)
-            rb = np.arange(2 * F).reshape(1, 2 * F)
-            srcb = np.where(rb < F, s_pre_b + np.arange(T).reshape(T, 1) * F + rb, -1)
-            mp[i_pre_b:i_pre_b + T * 2 * F] = srcb.reshape(-1)
-            # post: block s of tower t, output o, operand column c in [x | mean | max | min | std (| sum | var)] (modules/pna/pna_module.py:_post_maps)
-            w = np.full((T, S * F, KF), -1, dtype=np.int64)
-            o = np.arange(F).reshape(F, 1)
-            f = np.arange(F).reshape(1, F)
-            for t in range(T):
-                tb = s_post_w + t * F * cols
-                for s_ in range(S):
-                    rows = slice(s_ * F, (s_ + 1) * F)
-                    if s_ == 0:
-                        w[t, rows, 0:F] = tb + o * cols + f
-                    if s_ < first:
-                        continue
-                    for ai, a in enumerate(c0.aggregators):
-                        slot = _AGG_SLOT[a]
-                        w[t, rows, F + slot * F:F + (slot + 1) * F] = tb + o * cols + F + (s_ - first) * A * F + ai * F + f
-            mp[i_post_w:i_post_w + T * S * F * KF] = w.reshape(-1)
-            bb = np.full((T, S * F), -1, dtype=np.int64)
-            bb[:, :F] = s_post_b + np.arange(T).reshape(T, 1) * F + np.arange(F).reshape(1, F)
-            mp[i_post_b:i_post_b + T * S * F] = bb.reshape(-1)
-            for j, v in enumerate((i_pre_w, i_pre_b, i_post_w, i_post_b)):
-                cm.pna_img_off[l][j] = v
-        inv = np.full(n_src, -1, dtype=np.int64)
-        used = mp >= 0
-        inv[mp[used]] = np.nonzero(used)[0]
-        assert (inv >= 0).all(), "every tower weight sits in the images exactly once"
-        self.pna_map = torch.from_numpy(mp.astype(np.int32)).to(self.dev)
-        self.pna_inv = torch.from_numpy(inv.astype(np.int32)).to(self.dev)
-        self.pna_img = torch.zeros(n_img, dtype=torch.float32, device=self.dev)
-        # ---- gradient layout: per layer [lin_w, lin_b, bn_w, bn_b] (gt_pna_layer_bwd's order), then the flat tower storage
-        for l, (conv, bn) in enumerate(self.convs):
-            cm.off_conv[l] = block((conv.lin.weight, conv.lin.bias, bn.weight, bn.bias))
-            self.w3_weights.append(conv.lin.weight)
             desc = self.conv_desc[l]
-            desc.D, desc.T, desc.S = D, T, S
-            desc.agg_slots = K
-            ib = l * img_per_layer
-            base = self.pna_img.data_ptr()
-            desc.pre_w, desc.pre_b = base + 4 * cm.pna_img_off[l][0], base + 4 * cm.pna_img_off[l][1]
-            desc.post_w, desc.post_b = base + 4 * cm.pna_img_off[l][2], base + 4 * cm.pna_img_off[l][3]
-            desc.lin_w, desc.lin_b = conv.lin.weight.data_ptr(), conv.lin.bias.data_ptr()
-            desc.bn_w, desc.bn_b = bn.weight.data_ptr(), bn.bias.data_ptr()
-            _bn_fields(desc, bn, hyper=True)
+            desc.pre_w, desc.pre_b, desc.post_w, desc.post_b = (base + 4 * o for o in cm.pna_img_off[l])
         # the towers' re-stacked matrices get bf16x3 images too (grouped k_lin3: the T GEMMs of a tower stack in one launch on the
         # bf16 matrix pipe at fp32 accuracy); views of pna_img, whose contents the driver gathers before it builds the images
-        self.pna_tower_views = []
+        views = []
         if PNA_TOWER_IMAGES:
             for l in range(L):
-                for j, (rows_, cols_) in ((0, (2 * F, F)), (2, (S * F, KF))):
+                for j, (rows_, cols_) in ((0, (2 * F, F)), (2, (S * F, (1 + K) * F))):
                     o0 = int(cm.pna_img_off[l][j])
-                    for t in range(T):
-                        v = self.pna_img[o0 + t * rows_ * cols_:o0 + (t + 1) * rows_ * cols_].view(rows_, cols_)
-                        self.pna_tower_views.append(v)
+                    views += [self.pna_img[o0 + t * rows_ * cols_:o0 + (t + 1) * rows_ * cols_].view(rows_, cols_) for t in range(T)]
             # the bind table holds W_MAX_BOUND weights: when the tower views would overflow it they are the ones left out (the towers
             # then run the exact-fp32 tiled kernels) -- NOT every image of the model (ADVICE r5: the whole set silently fell back)
-            if len(self.w3_weights) + len(self.pna_tower_views) + 2 <= W_MAX_BOUND:   # (+ gnn2transformer, + a Linear node encoder)
-                self.w3_weights.extend(self.pna_tower_views)
-            else:
+            if len(self.w3_weights) + len(views) + 2 > W_MAX_BOUND:   # (+ gnn2transformer, + a Linear node encoder)
                 import warnings
                 warnings.warn("graphtrans_amd: %d PNA tower matrices do not fit the library's %d-entry weight-image table beside the "
-                              "model's other weights: the towers run on the exact-fp32 kernels" % (len(self.pna_tower_views), W_MAX_BOUND))
-                self.pna_tower_views = []
-        cm.off_pna_src = self.total
-        for p, o_ in tower_params:
-            self.params.append((p, self.total + o_))
-        self.total += n_src
-        cm.pna_src, cm.pna_img = flat.data_ptr(), self.pna_img.data_ptr()
-        cm.pna_map, cm.pna_inv = self.pna_map.data_ptr(), self.pna_inv.data_ptr()
-        cm.pna_n_img, cm.pna_n_src = n_img, n_src
-        for i, blk in enumerate(c0._blocks):
-            cm.pna_kinds[i] = self._SCALER_KIND[blk]
-        cm.pna_avg_log, cm.pna_avg_lin = float(c0.avg_deg["log"]), float(c0.avg_deg["lin"])
+                              "model's other weights: the towers run on the exact-fp32 kernels" % (len(views), W_MAX_BOUND))
+                views = []
+        return views
 
     def set_frozen(self, frozen):
         """The part of the plan that follows `requires_grad`: with gnn_node frozen the backward is stage 1 alone (gt_model_batch::
@@ -756,17 +386,6 @@ def _plan(model):
     return plan
 
 
-def frozen_pattern(model):
-    """Which parameters of `model` are frozen (requires_grad == False): "none", "gnn" -- exactly the parameters of model.gnn_node,
-    what epoch_callback's freeze_gnn leaves behind -- or "other" (a single conv, gnn2transformer, gnn_node plus a head, ...).
-    Pure: flags only, no device, no library call."""
-    frozen = {id(p) for p in model.parameters() if not p.requires_grad}
-    if not frozen:
-        return "none"
-    gnn = model_parts(model)[0]   # (a model without message passing has no "gnn" pattern)
-    return "gnn" if gnn is not None and frozen == {id(p) for p in gnn.parameters()} else "other"
-
-
 def eligible(model, batched_data, perturb):
     """True when the fused path covers this model / call (the static part is cached per model and mode)."""
     if not getattr(model, "fused", True):
@@ -811,7 +430,8 @@ def eligible(model, batched_data, perturb):
     if pos is not None and not (pos.dropout.p == 0 and pos.pe.is_cuda and pos.pe.dtype == torch.float32 and pos.pe.is_contiguous()):
         return False   # (changed since the static answer was cached: the module path raises GNNTransformer._packed_pe's message)
     x = batched_data.x
-    if type(ne) is torch.nn.Linear:
+    kind, tabs, _ = input_encoder(ne)
+    if kind == "linear":
         # (features that require a gradient go through the module path: the fused node only differentiates parameters)
         if not (x.is_cuda and x.dtype == torch.float32 and x.dim() == 2 and x.shape[1] == ne.in_features
                 and not x.requires_grad and getattr(batched_data, "node_depth", None) is None):
@@ -819,25 +439,24 @@ def eligible(model, batched_data, perturb):
     else:
         if not (x.is_cuda and x.dtype == torch.int64 and x.dim() == 2):
             return False
-        if hasattr(ne, "type_encoder"):   # ASTNodeEncoder reads columns 0, 1 of x and node_depth (dataset/utils.py:28-30)
+        if kind == "ast":   # ASTNodeEncoder reads columns 0, 1 of x and node_depth (dataset/utils.py:28-30)
             nd = getattr(batched_data, "node_depth", None)
             if x.shape[1] < 2 or nd is None or nd.numel() != x.shape[0]:
                 return False
-        elif x.shape[1] != len(ne.atom_embedding_list):
+        elif x.shape[1] != len(tabs):
             # e.g. the reference's `--feature simple` (dataset/mol.py:65-69) slices x to 2 columns: the fused kernels
             # index one column per table, so a different column count goes through the module path
             return False
     if gnn is None or hasattr(gnn, "layers"):   # no message passing / PNANodeEmbedding: no edge features on the path (modules/pna/pna_module.py:73)
         return True
     # edge features: the aggregate kernels read `edge_cols` values per edge at that pitch
-    ee = gnn.convs[0].edge_encoder
+    mode, edge = edge_encoder(gnn.convs[0])
     ea = getattr(batched_data, "edge_attr", None)
-    tabs = getattr(ee, "bond_embedding_list", None)
-    if tabs is not None:
-        if ea is None or ea.dim() != 2 or ea.shape[1] != len(tabs) or ea.dtype != torch.int64 or not ea.is_cuda:
+    if mode == "tables":
+        if ea is None or ea.dim() != 2 or ea.shape[1] != len(edge) or ea.dtype != torch.int64 or not ea.is_cuda:
             return False
-    elif isinstance(ee, torch.nn.Linear):
-        if ea is None or ea.dim() != 2 or ea.shape[1] != ee.in_features or not ea.is_cuda or not ea.is_floating_point():
+    elif mode == "linear":
+        if ea is None or ea.dim() != 2 or ea.shape[1] != edge[0].shape[1] or not ea.is_cuda or not ea.is_floating_point():
             return False
     return True
 
@@ -851,15 +470,7 @@ def _enc_only_call_ok(model, ne, perturb):
     sync = state(model).get("sync")
     if sync is not None and sync.active:
         return False
-    return perturb is None or type(ne) is not torch.nn.Linear
-
-
-def emb_dim(model):
-    """gnn_emb_dim (d_model for a model without message passing): the width of the node rows, and of a perturbation"""
-    gnn, enc, _ = model_parts(model)
-    if gnn is None:
-        return int(enc.d_model)
-    return int(gnn.layers[0].in_channels if hasattr(gnn, "layers") else gnn.convs[0].emb_dim)
+    return perturb is None or input_encoder(ne)[0] != "linear"
 
 
 def _perturb_ok(model, batched_data, perturb):
@@ -920,213 +531,27 @@ def _note_ddp_wrapper(parent, name, child):
 torch.nn.modules.module.register_module_module_registration_hook(_note_ddp_wrapper)
 
 
-def _frozen_ok(model):
-    """every parameter trainable, or -- only with `model.fused_freeze`, never in the read-out or the encoder-only mode -- exactly
-    gnn_node frozen"""
-    pat = frozen_pattern(model)
-    if readout_kind(model) or model_parts(model)[0] is None:
-        return pat == "none"
-    return pat == "none" or (pat == "gnn" and bool(getattr(model, "fused_freeze", False)))
-
-
 def _eligible_static(model):
-    from . import ops
-    from .modules.conv import GCNConv
-    from .modules.norm import BatchNorm1d
+    """The static half of `eligible`: what the module tree says (model_layout.structural_ok: the same for a CPU model), then where the
+    parameters live and the library's own question.  THE one blanket `except`: a model that is none of the families is not eligible."""
     try:
-        gnn = model_parts(model)[0]
-    except Exception:
-        return False
-    if gnn is None:
-        return _eligible_static_enc_only(model)
-    try:
-        ro = readout_kind(model)   # models.gnn.GNN: message passing -> sum / mean / max pooling -> heads (no PNA stack, JK = last only)
-    except Exception:
-        return False
-    if hasattr(gnn, "layers"):
-        return _eligible_static_pna_readout(model) if ro else _eligible_static_pna(model)
-    try:
-        if ro:
-            if gnn.JK != "last" or gnn.num_layer > MAXL:
-                return False
-        else:
-            enc = model.transformer_encoder
-            if not model._use_packed() or gnn.JK not in ("last", "cat"):
-                return False
-            if gnn.num_layer > MAXL or len(enc.transformer.layers) > MAXL or len(enc.transformer.layers) < 1:   # the driver's fixed-size tables
-                return False
-        D = gnn.convs[0].emb_dim
-        if D % 4:
-            return False
-        from .modules.conv import GINConv, tables_fit_lds
-        kinds = {type(conv) for conv in gnn.convs}
-        if len(kinds) != 1 or not (kinds <= {GCNConv, GINConv}):
-            return False
-        for conv, bn in zip(gnn.convs, gnn.batch_norms):
-            if not isinstance(bn, BatchNorm1d):
-                return False
-            if not (bn.affine and bn.track_running_stats and bn.momentum is not None):
-                return False
-            if isinstance(conv, GINConv):
-                m = list(conv.mlp)
-                if not (len(m) == 4 and isinstance(m[0], torch.nn.Linear) and isinstance(m[1], BatchNorm1d)
-                        and isinstance(m[3], torch.nn.Linear) and m[1].affine and m[1].track_running_stats
-                        and m[1].momentum is not None):
-                    return False
-            ee = conv.edge_encoder
-            tabs = getattr(ee, "bond_embedding_list", None)
-            if tabs is not None:
-                rows = sum(int(t.weight.shape[0]) for t in tabs)
-                if len(tabs) > 4 or not tables_fit_lds(rows, D):
-                    return False
-            elif isinstance(ee, torch.nn.Module):
-                if not (isinstance(ee, torch.nn.Linear) and ee.in_features <= 4 and ee.bias is not None):
-                    return False
-            else:
-                e = ee(None)
-                if not (isinstance(e, (int, float)) and e == 0):
-                    return False
-        if hasattr(gnn, "mlp_virtualnode_list"):
-            for seq in gnn.mlp_virtualnode_list:
-                m = list(seq)
-                if not (len(m) == 6 and isinstance(m[0], torch.nn.Linear) and isinstance(m[1], BatchNorm1d)
-                        and isinstance(m[3], torch.nn.Linear) and isinstance(m[4], BatchNorm1d)):
-                    return False
-        if not ro and model.gnn2transformer.weight.shape[1] % 4:
-            return False
-        return _eligible_static_rest(model)
+        return structural_ok(model) and _placement_ok(model)
     except Exception:
         return False
 
 
-def _eligible_static_rest(model):
-    """what every conv kind asks of the rest of the model: node encoder, encoder widths, head dim, FFN width, synchronised BatchNorm,
-    parameter dtype, frozen pattern (called inside the callers' try)"""
-    from .modules.norm import BatchNorm1d, any_sync
-    _, enc, ne = model_parts(model)
-    if type(ne) is torch.nn.Linear:
-        if ne.bias is None:
-            return False
-    elif not (hasattr(ne, "type_encoder") or hasattr(ne, "atom_embedding_list")):
-        return False
-    if hasattr(ne, "atom_embedding_list") and len(ne.atom_embedding_list) > 16:
-        return False
-    if enc is not None and not _encoder_ok(enc):
-        return False
-    # (synchronised BatchNorm -- statistics over all data-parallel ranks -- runs on this path too: the library's BatchNorm calls
-    # exchange their statistics through dist.BnSyncHook, installed around the pass; all of the model's BatchNorms or none)
-    bns = [m for m in model.modules() if isinstance(m, BatchNorm1d)]
-    if any_sync(*bns) and not all(getattr(b, "sync", False) for b in bns):
-        return False
-    if any_sync(*bns) and len({id(getattr(b, "sync_group", None)) for b in bns}) != 1:
-        return False
-    for p in model.parameters():
-        if not (p.is_cuda and p.dtype == torch.float32 and p.is_contiguous()):
-            return False
-    return _frozen_ok(model)
-
-
-def _encoder_ok(enc):
-    """what the encoder kernels ask of a TransformerNodeEncoder: activation, widths, head dim, FFN width"""
-    if enc.activation not in layers.ENC_ACT or enc.d_model % 8 or enc.compute_dtype not in (torch.float32, torch.bfloat16):
-        return False
+def _placement_ok(model):
+    """every parameter a contiguous fp32 tensor on the device, and a head dim the library's attention kernels take"""
+    enc = model_parts(model)[1]
     head_dim_ok = getattr(_lib.lib(), "gt_attn_head_dim_ok", None)   # (None: an A/B library of an earlier revision, GT_LIB_PATH)
-    if head_dim_ok is not None and not head_dim_ok(GT_F32, enc.d_model, enc.nhead):   # (the module path raises the library's own message)
-        return False
-    for mod in enc.transformer.layers:
-        if mod.linear1.weight.shape[0] % 8:
-            return False
-    return True
+    if enc is not None and head_dim_ok is not None and not head_dim_ok(GT_F32, enc.d_model, enc.nhead):
+        return False   # (the module path raises the library's own message)
+    return all(p.is_cuda and p.dtype == torch.float32 and p.is_contiguous() for p in model.parameters())
 
 
 def _eligible_static_enc_only(model):
-    """Transformer (models/transformer.py:20-115) on the driver's encoder-only mode: cls pooling, 1 .. MAXL encoder layers, and an input
-    encoder whose rows can be the token rows -- ASTNodeEncoder / AtomEncoder with at most 16 tables of at most 16384 rows each (the
-    sorted table backward, ops.EMBED_SORT_MAX_ROWS) and d_model columns, or nn.Linear(F, d_model) with a bias.  Every parameter
-    trainable: this mode has no frozen pattern."""
-    from .ops import EMBED_SORT_MAX_ROWS
-    try:
-        _, enc, ne = model_parts(model)
-        if model.graph_pooling != "cls" or enc.cls_embedding is None or not (1 <= len(enc.transformer.layers) <= MAXL):
-            return False
-        d = int(enc.d_model)
-        if type(ne) is torch.nn.Linear:
-            if ne.out_features != d:
-                return False
-        else:
-            if hasattr(ne, "type_encoder"):
-                tabs = [ne.type_encoder.weight, ne.attribute_encoder.weight, ne.depth_encoder.weight]
-            elif hasattr(ne, "atom_embedding_list"):
-                tabs = [e.weight for e in ne.atom_embedding_list]
-            else:
-                return False
-            if not (1 <= len(tabs) <= MAXT and all(t.dim() == 2 and t.shape[1] == d and 1 <= t.shape[0] <= EMBED_SORT_MAX_ROWS for t in tabs)):
-                return False
-        return frozen_pattern(model) == "none" and _eligible_static_rest(model)
-    except Exception:
-        return False
-
-
-def _eligible_static_pna(model):
-    """PNATransformer (models/pna_transformer.py:16-118) on the fused path: PNANodeEmbedding with the residual connection, towers
-    that divide the input, single-layer pre / post nets, packed token layout."""
-    gnn, enc = model.gnn_node, model.transformer_encoder
-    try:
-        if not (model.pooling in ("cls", "last") and getattr(model, "layout", "auto") != "padded" and len(enc.transformer.layers) > 0):
-            return False
-        if len(enc.transformer.layers) > MAXL or not _pna_convs_ok(gnn):
-            return False
-        if model.gnn2transformer.in_features != gnn.layers[0].in_channels:
-            return False
-        return _eligible_static_rest(model)
-    except Exception:
-        return False
-
-
-def _eligible_static_pna_readout(model):
-    """PNANet (models/pna.py:20-104) on the fused path: the PNA conv checks of `_eligible_static_pna`, nothing about an encoder, and
-    the widths the head kernels take (csrc/mlp_heads.hip)."""
-    gnn = model.gnn_node
-    try:
-        if not _pna_convs_ok(gnn):
-            return False
-        D = gnn.layers[0].in_channels
-        if head_kind(model) == 1:
-            l1, l2, l3 = model.mlp[0], model.mlp[2], model.mlp[4]
-            if not (l1.in_features == D and max(l1.out_features, l2.out_features) <= 64 and all(m.bias is not None for m in (l1, l2, l3))):
-                return False
-        else:
-            heads = list(model.graph_pred_linear_list)
-            if not (1 <= len(heads) <= 16 and D % 16 == 0 and D <= 512):
-                return False
-            if any(seq[0].in_features != D or seq[0].out_features != D or seq[0].bias is None or seq[2].bias is None for seq in heads):
-                return False
-        return _eligible_static_rest(model)
-    except Exception:
-        return False
-
-
-def _pna_convs_ok(gnn):
-    """what the driver's PNA stack asks of a PNANodeEmbedding (called inside the callers' try)"""
-    from .modules.norm import BatchNorm1d
-    from .modules.pna.pna_module import PNAConv, _AGG_SLOT
-    convs = list(gnn.layers)
-    if not convs or len(convs) > MAXL or not gnn.residual:
-        return False
-    c0 = convs[0]
-    for c in convs:
-        if not (isinstance(c, PNAConv) and c.divide_input and c.in_channels == c.out_channels == c0.in_channels and c.towers == c0.towers
-                and c.F_in == c.F_out and c.aggregators == c0.aggregators and c.scalers == c0.scalers and c.avg_deg == c0.avg_deg):
-            return False
-    if len(c0._blocks) > 8 or any(a not in _AGG_SLOT for a in c0.aggregators) or c0.in_channels > 1024:
-        return False
-    if any(b not in _Plan._SCALER_KIND for b in c0._blocks):
-        return False
-    for bn in gnn.batch_norms:
-        m = getattr(bn, "module", None)
-        if not (isinstance(m, BatchNorm1d) and m.affine and m.track_running_stats and m.momentum is not None):
-            return False
-    return not (c0.in_channels % 4 or c0.F_in % 4)
+    """`_eligible_static` of a `models.transformer.Transformer` (the driver's encoder-only mode); False for every other model"""
+    return _eligible_static(model) and model_parts(model)[0] is None
 
 
 # ---------------------------------------------------------------------------------------------------

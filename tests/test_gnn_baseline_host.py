@@ -383,7 +383,9 @@ INVALID = -1   # GT_ERR_INVALID_ARG
 
 
 def _driver_model(readout=2, L=3, D=32, Nh=15, has_vn=True):
-    """A gt_model as engine._Plan fills it for a GCN read-out model; device pointers are made-up addresses (never followed on the host)"""
+    """A gt_model as the plan fills it for a GCN read-out model, written out by hand: model_layout.ModelLayout (step 1 of a plan: offsets
+    and every other non-pointer field) and engine.bind_storage (step 2: pointers) build the real one, and
+    tests/test_model_layout_host.py holds it against this one; device pointers are made-up addresses (never followed on the host)"""
     from graphtrans_amd import engine, layers
     fake = 0x10000
     keep = []

@@ -388,8 +388,10 @@ def test_fixture_agrees_with_the_statement():
 # the driver's read-out mode with the PNA stack and the head kinds, host only (gt_model_prepare asks sizes: no device call)
 # ---------------------------------------------------------------------------------------------------------------------------------
 def _driver_model(head_kind=2, readout=2, L=3, D=32, T_out=7, pos=3, h1=35, h2=17):
-    """A gt_model as engine._Plan fills it for a PNANet: test_gnn_baseline_host._driver_model's struct (made-up device addresses, never
-    followed on the host) with the PNA stack in place of the GCN layers and the head block re-laid behind the tower parameters"""
+    """A gt_model as the plan fills it for a PNANet, by hand: test_gnn_baseline_host._driver_model's struct (made-up device addresses,
+    never followed on the host) with a schematic PNA stack in place of the GCN layers and the head block re-laid behind the tower
+    parameters.  The real one comes from model_layout.ModelLayout (step 1: offsets, shape) and engine.bind_storage (step 2: pointers);
+    tests/test_model_layout_host.py compares shape and head block with this one."""
     from graphtrans_amd import layers
     fake = 0x10000
     Nh = T_out * pos if head_kind == 2 else T_out

@@ -67,8 +67,10 @@ def test_abi_sizes_still_match_the_mirrors():
 
 
 def _enc_only_model(embed_kind=0, d=64, Nh=6, n_enc=2, tables=(11, 13)):
-    """A gt_model as engine._Plan fills it for the Transformer baseline; device pointers are made-up addresses (never followed on the
-    host).  Gradient layout: input encoder, cls, encoder layers, final norm, heads."""
+    """A gt_model as the plan fills it for the Transformer baseline, by hand; device pointers are made-up addresses (never followed on
+    the host).  Gradient layout: input encoder, cls, encoder layers, final norm, heads.  The real one comes from
+    model_layout.ModelLayout (step 1: offsets, shape) and engine.bind_storage (step 2: pointers); tests/test_model_layout_host.py holds
+    it against this one field by field."""
     from graphtrans_amd import engine, layers
     fake = 0x10000
     cm = engine.ModelDesc()

@@ -1,11 +1,14 @@
 """Everything the whole-model driver (csrc/model.hip, engine.py) computes, on a fixed grid of fused models, into one file:
-python tools/driver_dump.py OUT.pt [name filter]
+python tools/driver_dump.py OUT.pt [name filter] [--digest]
 
 For every entry of the grid in the fp32, mixed and bf16 modes: one training forward + backward (dropout on, fixed seeds), one eval
 forward, and the training step once more with the backward in its three stages (a one-rank GradSync that asks for them) -- logits,
 every gradient, every buffer (the BatchNorm statistics), and what gt_model_prepare answered (gt_model_sizes).  Two revisions of the
 driver that launch the same kernels in the same order write files whose tensors are torch.equal:
-python tools/driver_dump.py --compare A.pt B.pt"""
+python tools/driver_dump.py --compare A.pt B.pt
+--digest keeps a SHA-256 of every tensor's bytes (with dtype and shape) in the tensor's place: a file of a few hundred KB that
+compares the same way."""
+import hashlib
 import os
 import sys
 
@@ -124,7 +127,40 @@ def grid():
             return model, b, lambda out: losses.code2_loss(out, y)
         return build
 
+    def pnanet(msl):   # the read-out mode over the PNA stack: head kind 1 (max_seq_len None: the narrow MLP) or 2 (the position heads)
+        def build(dt):
+            from types import SimpleNamespace
+            from graphtrans_amd.models.pna import PNANet
+            a = SimpleNamespace(gnn_num_layer=3, gnn_emb_dim=64, gnn_dropout=0.25, gnn_residual=True, graph_pooling="mean", max_seq_len=msl,
+                                model_type="pna", aggregators=["mean", "max", "min", "std"],
+                                scalers=["identity", "amplification", "attenuation"], deg=torch.tensor([0, 40, 25, 9, 3]))
+            model = PNANet(50, ASTNodeEncoder(64, 98, 300, 20), None, a).to(DEV)
+            b = synth.code2_like(B=12, seed=5, num_nodeattributes=300).to(DEV)
+            y = labels(12, 5, 5)
+            return model, b, (lambda out: out.float().square().mean()) if msl is None else (lambda out: losses.code2_loss(out, y))
+        return build
+
+    def transformer(feat):   # the encoder-only mode (models.transformer.Transformer with fused_step): table and Linear input encoder
+        def build(dt):
+            from types import SimpleNamespace
+            from graphtrans_amd.models.transformer import Transformer
+            a = SimpleNamespace(d_model=64, nhead=4, dim_feedforward=128, transformer_dropout=0.1, transformer_activation="relu",
+                                num_encoder_layers=2, max_input_len=100, transformer_norm_input=True, graph_pooling="cls",
+                                max_seq_len=(3 if feat == "ast" else None), model_type="transformer", gnn_type="gcn", gnn_virtual_node=False,
+                                fused_step=True, compute_dtype=dt)
+            if feat == "ast":
+                model = Transformer(50, ASTNodeEncoder(64, 98, 300, 20), None, a).to(DEV)
+                b = synth.code2_like(B=12, seed=5, num_nodeattributes=300).to(DEV)
+                y = labels(12, 5, 5)
+                return model, b, lambda out: losses.code2_loss(out, y)
+            model = Transformer(2, torch.nn.Linear(37, 64), None, a).to(DEV)
+            b = synth.nci1_like(B=16, seed=3).to(DEV)
+            return model, b, lambda out: losses.tud_loss(out, b.y)
+        return build
+
     g["pna"] = pna
+    g["pnanet:mlp"], g["pnanet:positions"] = pnanet(None), pnanet(3)
+    g["transformer:ast"], g["transformer:linear"] = transformer("ast"), transformer("linear")
     for pool in ("sum", "mean", "max"):
         for kw in (dict(), dict(gnn_type="gin", gnn_virtual_node=False)):
             g[f"gnn:{pool}," + ident(kw)] = gnn(dict(graph_pooling=pool, **kw), 12, 5)
@@ -151,7 +187,7 @@ def asked(model, N, mm, dt):
     from graphtrans_amd import _lib, engine, ops
     from graphtrans_amd._lib import GT_BF16, GT_F32
     plan, L = engine._plan(model), _lib.lib()
-    if plan.kind == "pna":
+    if plan.kind == "pna" or getattr(plan, "enc_only", False):
         return {}
     tok_bf16 = dt == torch.bfloat16
     imgs = None
@@ -175,7 +211,7 @@ def asked(model, N, mm, dt):
     return a
 
 
-def main(out_path, only=None):
+def main(out_path, only=None, digest=False):
     from graphtrans_amd import _lib, engine, ops
     from graphtrans_amd.dist import GradSync
 
@@ -243,6 +279,9 @@ def main(out_path, only=None):
                 r["sizes"] = [list(s) for s in sizes]
                 torch.cuda.synchronize()
             res[key] = {k: (v.cpu() if torch.is_tensor(v) else v) for k, v in r.items()}
+            if digest:
+                res[key] = {k: (f"{v.dtype} {tuple(v.shape)} " + hashlib.sha256(v.contiguous().reshape(-1).view(torch.uint8).numpy().tobytes()).hexdigest()
+                                if torch.is_tensor(v) else v) for k, v in res[key].items()}
             print(key, "N", r.get("N"), "eligible", r["eligible"], "stages", r.get("staged.ranges"), "asked", r.get("asked"), "sizes", r.get("sizes"), flush=True)
     ops.set_matmul_dtype(torch.float32)
     torch.save(res, out_path)
@@ -252,4 +291,5 @@ def main(out_path, only=None):
 if __name__ == "__main__":
     if sys.argv[1] == "--compare":
         sys.exit(compare(sys.argv[2], sys.argv[3]))
-    main(sys.argv[1], sys.argv[2] if len(sys.argv) > 2 else None)
+    rest = [a for a in sys.argv[2:] if a != "--digest"]
+    main(sys.argv[1], rest[0] if rest else None, digest="--digest" in sys.argv)
